@@ -9,12 +9,19 @@ under a launcher (RANK / WORLD_SIZE set, the driver's form) WORLD_SIZE must equa
 A "step" = one pass of the hot path over one synthetic KITTI-shaped pair per GPU: forward + reprojection loss + EPE/bad3 +
 full backward + momentum update (the loop body of Stereo_Online_Adaptation.py:178-253), replayed as a captured hipGraph with
 the inputs resident in HBM.  Streams are independent (private models): no data-path collective, weak scaling.  After W warm-up
-steps the K-step region is timed --repeats times (each bracketed by barrier + synchronize, MAX over ranks); `value` is computed
-from the MEDIAN region, all regions are listed under `timing`.  Rank 0 prints ONE JSON line.
+steps exactly K steps are timed (bracketed by barrier + synchronize, MAX over ranks); `ms_per_step` = that region / K.
+--repeats R times the K-step region R times and takes the MEDIAN region; --min-region-seconds S repeats the K-step block inside
+a region until it lasts >= S seconds.  Rank 0 prints ONE JSON line.
+
+A plain run does only that (set up, warm up, time, print).  --full adds the side measurements: roofline and kernel families,
+the other arithmetic modes (`paths`), the N-step drift report, `step_surface`, the side configurations (`configs`), the
+disparity against the fp32 CPU oracle (`epe_vs_oracle`) and the CPU baselines.  --dump-outputs DIR writes what the last timed
+step computed (disparity, loss, EPE, bad3, the adapted weights) as DIR/<name>.npy; inputs and weights are seeded, so two
+builds run with the same arguments can be compared output for output.
 
 Default arithmetic = 'mixed': the forward pass stays within the north-star tolerance (1e-3 px EPE vs the fp32 CPU oracle:
-split-bf16 MFMA on the large 3x3 layers, exact fp32 MFMA elsewhere), gradients run on bf16 MFMA.  `paths` lists the same
-step in the other arithmetic modes (exact fp32; plain bf16 = faster but OUTSIDE the tolerance) with their own EPE.
+split-bf16 MFMA on the large 3x3 layers, exact fp32 MFMA elsewhere), gradients run on bf16 MFMA.  `paths` (--full) lists the
+same step in the other arithmetic modes (exact fp32; plain bf16 = faster but OUTSIDE the tolerance) with their own EPE.
 """
 import argparse
 import json
@@ -318,6 +325,32 @@ def inner_reps(dev, dist, one_step, steps, min_seconds):
     return max(1, int(-(-min_seconds // max(t, 1e-6))))
 
 
+DUMP_BUDGET_BYTES = 64 << 20
+
+
+def engine_outputs(e, suffix=""):
+    """what a caller of the step receives from engine `e` after it (Adapter.step's disparity / loss / epe / bad3, plus the adapted weights)"""
+    return [("disparity" + suffix, e.pred), ("loss" + suffix, e.res_loss[0:1]), ("epe" + suffix, e.res_met[0:1]), ("bad3" + suffix, e.res_met[1:2]),
+            ("weights" + suffix, e.params.w)]
+
+
+def dump_outputs(d, arrays):
+    """--dump-outputs DIR: every (name, tensor / array) as DIR/<name>.npy in float32, DUMP_BUDGET_BYTES in all.  When they hold more, the smallest arrays
+    are kept whole and the larger ones share what is left, each as a sample of its flattened elements drawn with a fixed seed (the same indices in every run
+    of the same shapes)."""
+    import numpy as np
+    os.makedirs(d, exist_ok=True)
+    arrays = [(k, np.ascontiguousarray((v.detach().float().cpu().numpy() if hasattr(v, "detach") else np.asarray(v)), dtype=np.float32)) for k, v in arrays]
+    budget, left = DUMP_BUDGET_BYTES // 4, len(arrays)
+    for k, a in sorted(arrays, key=lambda kv: kv[1].size):
+        keep = min(a.size, budget // left)
+        if keep < a.size:
+            a = a.reshape(-1)[np.sort(np.random.default_rng(0).choice(a.size, keep, replace=False))]
+        np.save(os.path.join(d, k + ".npy"), a)
+        budget, left = budget - keep, left - 1
+    _log("outputs of the last timed step -> %s (%s)" % (d, ", ".join(k for k, _ in arrays)))
+
+
 def bench_mad(args, lib, dev, rank, world, dist):
     """BASELINE config 3: MAD modular adaptation through the reference's own API surface (Nets.get_stereo_net +
     Adapter.step): per step the host samples a block (Sampler/sampler_factory.py), replays that block's captured
@@ -344,6 +377,8 @@ def bench_mad(args, lib, dev, rank, world, dist):
         args.rccl["in_graph"] = ad.comm is not None
     for i in range(len(cfg)):
         ad._plan((i,))                       # compile + capture every block's plan outside the timed region
+    import numpy as np
+    np.random.seed(0)                        # the block draws (numpy's global RandomState): the same sequence in every run
     last = {}
 
     def one_step():
@@ -353,6 +388,10 @@ def bench_mad(args, lib, dev, rank, world, dist):
         one_step()
     inner = inner_reps(dev, dist, one_step, args.steps, args.min_region_seconds)
     regions = timed_regions(dev, dist, one_step, args.steps, args.repeats, inner)
+    if args.dump_outputs and rank == 0:
+        o = last["o"]
+        dump_outputs(args.dump_outputs, [("disparity", o["disparity"]), ("loss", [o["loss"]]), ("epe", [o["epe"]]), ("bad3", [o["bad3"]]),
+                                         ("weights", ad.eng.params.w)])
     if dist is not None:
         dist.destroy_process_group()
     if rank == 0:
@@ -750,14 +789,20 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=100)
     ap.add_argument("--warmup", type=int, default=10)
-    ap.add_argument("--repeats", type=int, default=5, help="how many times the K-step region is timed (value = the median region)")
+    ap.add_argument("--repeats", type=int, default=1, help="how many times the K-step region is timed (value = the median region; default 1: exactly --steps timed steps)")
     ap.add_argument("--graph-copies", type=int, default=1, help="executable graphs of the step, launched in turn (experiment)")
     ap.add_argument("--step-sync", default="auto", choices=["auto", "none", "stream"],
                     help="none: the K steps of a region are enqueued back to back; stream: the host synchronises the step's stream after every step (what a consumer of the "
                          "disparity does); auto: stream for the single-stream private MADNet FULL step (measured faster), none elsewhere")
-    ap.add_argument("--min-region-seconds", type=float, default=1.0,
-                    help="every timed region is lengthened to at least this many seconds by repeating the K-step block inside it (0 = exactly K steps)")
-    ap.add_argument("--drift-steps", type=int, default=100, help="N-step drift report: 'mixed' vs the fp32 engine after 10 and N adaptation steps on a frame-shifted synthetic video (0 = skip)")
+    ap.add_argument("--min-region-seconds", type=float, default=0.0,
+                    help="every timed region is lengthened to at least this many seconds by repeating the K-step block inside it (default 0 = exactly K steps)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the side measurements of the default line (off by default: a plain run sets up, warms up, times the K steps and prints): roofline "
+                         "and kernel families, `paths`, `drift`, `step_surface`, `configs`, `epe_vs_oracle` and the CPU baselines; the --no-* options below trim them")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last one computed (disparity, loss, epe, bad3, adapted weights) as DIR/<name>.npy, float32, "
+                         "<= 64 MB in all (larger arrays: a fixed, seeded sample of their elements)")
+    ap.add_argument("--drift-steps", type=int, default=100, help="--full: N-step drift report: 'mixed' vs the fp32 engine after 10 and N adaptation steps on a frame-shifted synthetic video (0 = skip)")
     ap.add_argument("--mode", default="FULL", choices=["FULL", "NONE", "MAD"])
     ap.add_argument("--block-config", default="MadNet_piramid_only.json", help="MAD mode: file under block_config/")
     ap.add_argument("--model", default="madnet", choices=["madnet", "dispnet"])
@@ -800,11 +845,13 @@ def main():
     ap.add_argument("--no-configs", action="store_true",
                     help="skip the `configs` block of the default line (BASELINE configs 3 / 4 = MAD / DispNet, 4 private-model streams, their batched ceiling) and the "
                          "extra correlation rooflines")
-    ap.add_argument("--extras-on-cpu", action="store_true", help="--device cpu only (tests): also walk the roofline / paths / configs code of the default line on the emulator")
+    ap.add_argument("--extras-on-cpu", action="store_true", help="--full --device cpu only (tests): also walk the roofline / paths / configs code of the default line on the emulator")
     ap.add_argument("--detail", default=None, metavar="NAME", help="file name of the complete record (default bench_detail.json; written next to bench.py and into gpurun_out/)")
     ap.add_argument("--device", default="cuda", choices=["cuda", "cpu"],
                     help="cpu = plumbing test of the launcher path only (emulator library via MADNET_HIP_LIB, gloo); never a result")
     args = ap.parse_args()
+    if args.extras_on_cpu and not args.full:
+        ap.error("--extras-on-cpu walks the side measurements of --full: give --full too")
     if args.detail:
         global DETAIL_FILE
         DETAIL_FILE = os.path.basename(args.detail)
@@ -971,6 +1018,7 @@ def main():
     one_step, plan = make_step(eng)
     _log("engine built (%s), %d ops, graph=%s" % (args.precision, plan.n, use_graph))
     CS = args.concurrent_streams
+    more_engines = []                                  # --concurrent-streams: the other private models
     if CS > 1:
         assert dev.kind == "cuda" and not shared and use_graph, "--concurrent-streams needs hipGraph replay on a GPU, private models"
         from madnet_hip.plan import MultiPlan
@@ -1033,11 +1081,16 @@ def main():
             one_step()
         dev.sync_stream()
         inner = inner_reps(dev, dist, one_step, args.steps, args.min_region_seconds)
-        with BoxSampler(dev.index) as box_sampler:
+        with (BoxSampler(dev.index) if args.full else _Null()) as box_sampler:          # (the sysfs samples feed --full's `box` only)
             regions = timed_regions(dev, dist, one_step, args.steps, args.repeats, inner)
     tb = timing_block(regions, args.steps, inner)
     ms = tb["ms_per_step_median"]
     _log("timed regions done: median %.3f ms/step (min %.3f, max %.3f)" % (ms, tb["ms_per_step_min"], tb["ms_per_step_max"]))
+    if args.dump_outputs and rank == 0:
+        outs = engine_outputs(eng)
+        for i, e_i in enumerate(more_engines, 1):
+            outs += engine_outputs(e_i, "_stream%d" % i)
+        dump_outputs(args.dump_outputs, outs)
 
     shared_info = None
     if shared and hasattr(one_step, "collectives_only"):
@@ -1113,7 +1166,7 @@ def main():
         out["rccl"] = rccl
     if args.stamps > 0 and rank == 0 and not dispnet and not shared and CS == 1 and use_graph:
         out["tail"] = BT.tail_stamps(lib, E, mk, feed, args, dev, ms)
-    if rank == 0 and world == 1 and dispnet and SB == 1 and dev.kind == "cuda" and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and dispnet and SB == 1 and dev.kind == "cuda" and not args.no_cpu_baseline:
         # DispNet: disparity of the run's arithmetic mode against the fp32 CPU oracle on the bench pair (the same check MADNet's line carries)
         from oracle import dispnet as OD
         wt_ = {k: torch.from_numpy(v.copy()) for k, v in wn.items()}
@@ -1126,8 +1179,8 @@ def main():
         out["epe_tolerance"] = 1e-3
         out["within_tolerance"] = out["epe_vs_oracle"] <= 1e-3
         del e0
-    extras = rank == 0 and world == 1 and not dispnet and SB == 1 and CS == 1 and not shared and (dev.kind == "cuda" or args.extras_on_cpu) and args.mode == "FULL"
-    if args.extras_on_cpu:
+    extras = args.full and rank == 0 and world == 1 and not dispnet and SB == 1 and CS == 1 and not shared and (dev.kind == "cuda" or args.extras_on_cpu) and args.mode == "FULL"
+    if extras and args.extras_on_cpu:
         BT.WARMUP_LAUNCHES, BT.TABLE_REPS = 0, 1
     if extras:
         if not args.no_roofline:

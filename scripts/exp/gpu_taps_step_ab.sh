@@ -2,7 +2,7 @@
 # Whole-step A/B of the all-taps filter-gradient kernel with per-kernel timelines of one replayed step (default vs MH_WGRAD_TAPS=1): where the step gets
 # slower although the kernel is faster stand-alone (profiles/r02_microbench_wgrad_taps.txt).  ~1.5 GPU-minutes.
 TAG=${1:-taps_ab}; OUT=gpurun_out/$TAG; mkdir -p $OUT; export TMPDIR=/tmp
-B="--no-paths --no-cpu-baseline --no-roofline --no-step-surface"
+B="--no-paths --no-cpu-baseline --no-roofline --no-step-surface --min-region-seconds 1"      # (regions of >= 1 s, as these A/B numbers were taken)
 for V in default taps; do
   E=""; [ $V = taps ] && E="MH_WGRAD_TAPS=1"
   env $E timeout 120 python bench.py $B --repeats 3 --steps 100 2>/dev/null | tail -1 > $OUT/bench_$V.json

@@ -1,4 +1,5 @@
 mkdir -p gpurun_out/r4n; B="--no-paths --no-cpu-baseline --no-roofline --no-step-surface --drift-steps 0 --repeats 3 --steps 100 --stamps 20"
+B="$B --min-region-seconds 1"      # (regions of >= 1 s, as these A/B numbers were taken)
 run() { n=$1; shift; python bench.py $B "$@" 2>gpurun_out/r4n/$n.err | tail -1 > gpurun_out/r4n/$n.json; }
 run base
 run prog432 --set "engine.PYR_FLUSH_BEFORE=(4,3,2)"

@@ -8,7 +8,7 @@ TAG=${1:-${ROUND}final}; OUT=gpurun_out/$TAG; mkdir -p $OUT; export TMPDIR=/tmp;
 R=$GRAFT_REPO_ROOT
 bench() {  # bench <name> <args...>: the line -> $OUT/bench_<name>.json, the complete record -> $OUT/bench_<name>_detail.json
   local n=$1; shift
-  timeout 900 python bench.py "$@" --detail bench_${n}_detail.json 2>>$OUT/bench.err | tail -1 > $OUT/bench_$n.json
+  timeout 900 python bench.py --repeats 5 --min-region-seconds 1 "$@" --detail bench_${n}_detail.json 2>>$OUT/bench.err | tail -1 > $OUT/bench_$n.json
   mv -f bench_${n}_detail.json $OUT/ 2>/dev/null; rm -f gpurun_out/bench_${n}_detail.json
 }
 if [ "$SKIP_PMC" != "1" ]; then
@@ -20,10 +20,10 @@ if [ "$SKIP_TESTS" != "1" ]; then   # (RCCL prints a version banner through C st
   grep -E "passed|failed|error" $OUT/pytest_gpu.log | tail -3 >> $OUT/pytest_gpu.txt; cat $OUT/pytest_gpu.txt
 fi
 timeout 300 python -c "import __graft_entry__ as g; g.smoke()" > $OUT/smoke.txt 2>&1; tail -3 $OUT/smoke.txt
-# the driver's own command, stdout kept whole (the ONE line, < 6 KB)
-python3 bench.py --gpus 1 --steps 20 --warmup 5 > $OUT/bench_default.json 2>>$OUT/bench.err; cp bench_detail.json $OUT/bench_default_detail.json
+# the default line with every side measurement (--full) and the median of five >= 1 s regions, stdout kept whole (the ONE line, < 6 KB)
+python3 bench.py --gpus 1 --steps 20 --warmup 5 --full --repeats 5 --min-region-seconds 1 > $OUT/bench_default.json 2>>$OUT/bench.err; cp bench_detail.json $OUT/bench_default_detail.json
 wc -c $OUT/bench_default.json
-bench default_stamps --steps 20 --warmup 5 --stamps 20
+bench default_stamps --steps 20 --warmup 5 --stamps 20 --full
 if [ "$SKIP_VARIANTS" != "1" ]; then
   Q="--no-paths --no-cpu-baseline --no-roofline --no-step-surface --no-configs --drift-steps 0"
   bench mad --mode MAD $Q

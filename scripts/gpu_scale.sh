@@ -8,7 +8,7 @@ MAXG=${1:-8}; STEPS=${2:-50}; WARM=${3:-10}
 OUT=$PWD/gpurun_out/scale; mkdir -p $OUT
 export HSA_ENABLE_IPC_MODE_LEGACY=0 MASTER_ADDR=127.0.0.1
 HAVE=$(python -c "import torch; print(torch.cuda.device_count())" 2>/dev/null || echo 0)
-COMMON="--steps $STEPS --warmup $WARM --no-cpu-baseline --no-roofline --no-paths --no-step-surface --drift-steps 0"
+COMMON="--steps $STEPS --warmup $WARM --repeats 5 --min-region-seconds 1 --no-cpu-baseline --no-roofline --no-paths --no-step-surface --drift-steps 0"
 PORT=29610
 run() {   # tag, n, extra args
   local tag=$1 n=$2; shift 2

@@ -14,7 +14,7 @@ for item in $SWEEP; do
       ?*) extra="$extra --$a" ;;
     esac
   done
-  env $envs timeout 200 python bench.py $B --repeats 3 --steps 100 $extra 2>$OUT/$name.err | tail -1 > $OUT/$name.json
+  env $envs timeout 200 python bench.py $B --repeats 3 --min-region-seconds 1 --steps 100 $extra 2>$OUT/$name.err | tail -1 > $OUT/$name.json
   python - <<PY
 import json
 try:

@@ -1,11 +1,14 @@
 """`bench.py --gpus N` launcher path without a GPU: bench.py re-launches itself under torch.distributed.run (2 ranks), the
 ranks rendezvous over gloo on 127.0.0.1, each runs one emulated step (MADNET_HIP_LIB -> tests/emul library, --device cpu:
 plumbing only, never a result), the region time is MAX-reduced over the ranks and rank 0 prints the ONE JSON line with
-n_gpus = 2.  A launcher that starts a different world size than --gpus must fail loudly."""
+n_gpus = 2.  A launcher that starts a different world size than --gpus must fail loudly.  A plain run times exactly --steps steps, and
+--dump-outputs writes what its last step computed."""
 import json
 import os
 import subprocess
 import sys
+
+import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -127,3 +130,85 @@ def test_bench_line_fits_the_drivers_tail_and_parses(capsys, tmp_path, monkeypat
     assert d["drift"] == {"step_10": 0.0142, "step_100": 0.085}
     det = json.load(open(os.path.join(str(tmp_path), d["detail"])))
     assert det["kernel_families"][59]["kernel"].endswith(" 59") and det["value"] == full["value"]        # the complete record, full doubles
+
+
+def _bench_line(args, env=None, timeout=900):
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py")] + args, env=env, capture_output=True, text=True, timeout=timeout)
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = [ln for ln in r.stdout.strip().split("\n") if ln.startswith("{")]
+    assert len(lines) == 1, r.stdout[-2000:]
+    return json.loads(lines[0])
+
+
+def _load_dump(d):
+    import numpy as np
+    return {k: np.load(os.path.join(d, k + ".npy")) for k in ("disparity", "loss", "epe", "bad3", "weights")}
+
+
+def test_bench_plain_run_times_exactly_steps_and_dumps_outputs(tmp_path):
+    """A plain run times exactly --steps steps in one region, and --dump-outputs writes what its last step computed.  The inputs and weights are
+    seeded: 2 timed steps after none of warm-up and 1 timed step after 1 of warm-up leave the same state, bit for bit.  (That a plain run leaves
+    the side measurements out is checked on the GPU, where they used to run by default.)"""
+    import numpy as np
+    env = _env()
+    common = ["--gpus", "1", "--device", "cpu", "--height", "60", "--width", "100"]
+    a = _bench_line(common + ["--steps", "2", "--warmup", "0", "--dump-outputs", str(tmp_path / "a")], env)
+    b = _bench_line(common + ["--steps", "1", "--warmup", "1", "--dump-outputs", str(tmp_path / "b")], env)
+    for d, k in ((a, 2), (b, 1)):
+        assert d["steps"] == k and d["timing"]["repeats"] == 1 and d["timing"]["timed_steps_per_repeat"] == k and d["ms_per_step"] > 0
+    oa, ob = _load_dump(str(tmp_path / "a")), _load_dump(str(tmp_path / "b"))
+    assert oa["disparity"].shape == (1, 60, 100) and oa["weights"].size == 3826088 and all(v.dtype == np.float32 for v in oa.values())
+    assert abs(oa["loss"][0] - a["config"]["final_loss"]) <= 1e-5 * abs(a["config"]["final_loss"])
+    assert abs(oa["epe"][0] - a["config"]["epe_vs_synthetic_gt"]) <= 1e-5 * abs(a["config"]["epe_vs_synthetic_gt"])
+    for k in oa:
+        assert np.array_equal(oa[k], ob[k]), k
+
+
+def test_bench_mad_run_dumps_outputs_of_seeded_block_draws(tmp_path):
+    """--mode MAD (host block sampling through numpy's global RandomState, seeded by bench.py): the dump holds what Adapter.step returned for the last
+    timed step plus the adapted weights, and 2 + 0 / 1 + 1 timed / warm-up steps draw the same blocks and leave the same state, bit for bit."""
+    import numpy as np
+    env = _env()
+    common = ["--gpus", "1", "--device", "cpu", "--mode", "MAD", "--height", "60", "--width", "100"]
+    a = _bench_line(common + ["--steps", "2", "--warmup", "0", "--dump-outputs", str(tmp_path / "a")], env)
+    b = _bench_line(common + ["--steps", "1", "--warmup", "1", "--dump-outputs", str(tmp_path / "b")], env)
+    assert "MAD" in a["metric"] and a["timing"]["timed_steps_per_repeat"] == 2 and b["timing"]["timed_steps_per_repeat"] == 1
+    oa, ob = _load_dump(str(tmp_path / "a")), _load_dump(str(tmp_path / "b"))
+    assert oa["disparity"].shape == (1, 60, 100) and oa["weights"].size == 3826088
+    assert abs(oa["loss"][0] - a["config"]["final_loss"]) <= 1e-5 * abs(a["config"]["final_loss"])
+    for k in oa:
+        assert np.array_equal(oa[k], ob[k]), k
+
+
+def test_bench_extras_on_cpu_needs_full():
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--device", "cpu", "--extras-on-cpu"], env=_env(), capture_output=True, text=True, timeout=300)
+    assert r.returncode == 2 and "--full" in r.stderr
+
+
+def test_bench_dump_keeps_small_arrays_whole_and_samples_large_ones(tmp_path, monkeypatch):
+    import numpy as np
+    sys.path.insert(0, ROOT)
+    import bench
+    monkeypatch.setattr(bench, "DUMP_BUDGET_BYTES", 4 * 1000)
+    big, mid = np.arange(5000, dtype=np.float64), np.arange(300, dtype=np.float32).reshape(3, 100)
+    for sub in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / sub), [("big", big), ("mid", mid), ("one", [2.5])])
+    got = {k: np.load(str(tmp_path / "a" / (k + ".npy"))) for k in ("big", "mid", "one")}
+    assert got["one"].tolist() == [2.5] and np.array_equal(got["mid"], mid) and got["big"].dtype == np.float32
+    assert got["big"].size == 1000 - 300 - 1 and np.all(np.diff(got["big"]) > 0) and set(got["big"].tolist()) <= set(big.tolist())
+    assert np.array_equal(got["big"], np.load(str(tmp_path / "b" / "big.npy")))          # the same sample in every run
+
+
+@pytest.mark.gpu
+def test_bench_plain_run_on_gpu_dumps_the_timed_step(hip, tmp_path):
+    """The plain benchmark command on the MI355X: exactly --steps timed steps, no side measurements, the full-size outputs of the last step."""
+    import numpy as np
+    d = _bench_line(["--gpus", "1", "--steps", "3", "--warmup", "2", "--dump-outputs", str(tmp_path)], timeout=600)
+    assert d["n_gpus"] == 1 and d["steps"] == 3 and d["timing"]["timed_steps_per_repeat"] == 3 and d["timing"]["repeats"] == 1
+    assert d["config"]["launch"] == "hipGraph replay"
+    for key in ("roofline", "roofline_corr", "cpu_baseline", "paths", "drift", "step_surface", "configs", "epe_vs_oracle", "box"):
+        assert key not in d, key                      # --full only (a plain run printed them all before --full existed)
+    assert abs(d["value"] - 1e3 / d["ms_per_step"]) <= 1e-4 * d["value"]
+    o = _load_dump(str(tmp_path))
+    assert o["disparity"].shape == (1, 375, 1242) and np.isfinite(o["disparity"]).all() and (o["disparity"] != 0).mean() >= 0.25
+    assert abs(o["loss"][0] - d["config"]["final_loss"]) <= 1e-5 * abs(d["config"]["final_loss"]) and np.isfinite(o["weights"]).all()
