@@ -215,7 +215,7 @@ class Adapter(object):
                 plans[2].launch(self.lib, sh)
             elif self.shared:
                 # ONE collective per contiguous gradient range; the loss result sits right behind the gradient buffer
-                # (engine.Params.g), so gradients + loss travel together when the last range ends there.  Sums; the 1/world factors
+                # (params.Params.g), so gradients + loss travel together when the last range ends there.  Sums; the 1/world factors
                 # are applied by the momentum kernel (grad_scale) and on the host (loss).
                 P = eng.params
                 rng = P.ranges(self._train_vars(key))

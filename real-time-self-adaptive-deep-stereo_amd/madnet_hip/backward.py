@@ -6,13 +6,6 @@ from . import ops
 from .netdef import PYR, EST, CTX, LEVELS, FEAT, ALPHA, pyr_name, est_name, ctx_name, _merge_ranges      # noqa: F401
 
 
-def ops_fill(lib, t, off, count):
-    """record/launch a zero fill of t.flatten()[off:off+count]."""
-    import ctypes as C
-    flat = t.reshape(-1)
-    lib.fill(C.c_void_p(flat.data_ptr() + 4 * off), count, 0.0, None)
-
-
 class BackwardRecorder(object):
     def _train_flags(self, train_vars, bulkhead):
         tv = set(train_vars)
@@ -57,11 +50,11 @@ class BackwardRecorder(object):
             lib.lane = 1
         try:
             for o, c in P.ranges([v for v in train_vars if not (tail_lane and v in tail_vars)]):
-                ops_fill(lib, P.g, o, c)
+                ops.fill(lib, P.g, o, c)
             if tail_lane:
                 lib.lane = tail_lane
                 for o, c in P.ranges(tail_vars):
-                    ops_fill(lib, P.g, o, c)
+                    ops.fill(lib, P.g, o, c)
         finally:
             if g_side:
                 lib.lane = 0
@@ -72,7 +65,7 @@ class BackwardRecorder(object):
         first_writer = self.sched.FIRST_WRITER and self.sched.FUSE_BACK and self.warping
         prezero = self.sched.ONE_FILL and self.warping and not bulkhead and not first_writer
         if prezero:
-            ops_fill(lib, self.dF_levels, 0, self.dF_levels.numel())
+            ops.fill(lib, self.dF_levels, 0, self.dF_levels.numel())
         written = set()                     # gradient buffers that already hold a contribution
         if prezero:
             for i in FEAT.values():
@@ -135,7 +128,7 @@ class BackwardRecorder(object):
                     items, casts, todo = [], [], []
                     for xv, dzv, dw, db, stride, dil in pending:
                         if ops.wgrad_stream_ok(xv, dzv, dw, stride, dil) and xv.npix >= self.stream_min_pix:
-                            items.append((self._shadow(xv, casts), self._shadow(dzv, casts), dw, db, dil))
+                            items.append((self.images.queue_cast(xv, casts), self.images.queue_cast(dzv, casts), dw, db, dil))
                         else:
                             todo.append((xv, dzv, dw, db, stride, dil))
                     ops.shadow_cast(lib, casts, self.dev, r.keep)
@@ -199,12 +192,8 @@ class BackwardRecorder(object):
                 if wbt is not None and dzs is not None and (x_act is None or mks is not None):
                     # one-plane walk of the planes kernel: dz from its shadow, the mask from the activation's hi plane; the result leaves as a shadow
                     # (always: the next input gradient stages it) and, until the post-pass proves that nothing reads it, as fp32
-                    key = (dxv.ptr, dxv.B, dxv.H, dxv.W, dxv.C)
-                    sh = self.shadows.get(key)
-                    if sh is None:
-                        sh = self.shadows[key] = ops.Shadow(dxv.B, dxv.H, dxv.W, dxv.C, self.dev)
-                    ops.conv2d_planes_bwd(lib, dzs, self.W_(base), wbt, dx=dxv, dx_shadow=sh, mask_shadow=mks, mask_alpha=ALPHA, dil=dil)
-                    self._fresh.add(key)
+                    ops.conv2d_planes_bwd(lib, dzs, self.W_(base), wbt, dx=dxv, dx_shadow=self.images.shadow(dxv), mask_shadow=mks, mask_alpha=ALPHA, dil=dil)
+                    self.images.mark(dxv)
                     return
                 ops.conv2d_dgrad(lib, dzv, self.W_(base), dxv, stride=stride, dil=dil, accumulate=acc,
                                  mask_ref=x_act, mask_alpha=ALPHA, wb=self.Wd_(base),
@@ -317,7 +306,7 @@ class BackwardRecorder(object):
                 dFr = self._half(self.dF[f], True)
                 fresh = not acc_flag(("F", f, 1))
                 if fresh:
-                    ops_fill(lib, self.dF[f][B:], 0, self.dF[f][B:].numel())
+                    ops.fill(lib, self.dF[f][B:], 0, self.dF[f][B:].numel())
                 ops.warp_bwd(lib, self._fv(self.dRw[k]), self._half(self.F[f], True), self.u[k], dFr,
                              du=du, acc_u=True)
                 self._det_flush(lib, self.dF[f][B:], self.det_dF if self.deterministic else None, self.dF_levels)
@@ -344,9 +333,9 @@ class BackwardRecorder(object):
             # features that feed only the cost volume still need their own leaky gradient
             if ("Fd", top) not in written:
                 if ("F", top, 0) not in written:
-                    ops_fill(lib, self.dF[top][:B], 0, self.dF[top][:B].numel())
+                    ops.fill(lib, self.dF[top][:B], 0, self.dF[top][:B].numel())
                 if ("F", top, 1) not in written:
-                    ops_fill(lib, self.dF[top][B:], 0, self.dF[top][B:].numel())
+                    ops.fill(lib, self.dF[top][B:], 0, self.dF[top][B:].numel())
                 ops.leaky_bwd(lib, self._fv(self.dF[top]), self._fv(self.F[top]), ALPHA)
             for i in range(top, 0, -1):
                 if not pyr_need[i]:
@@ -358,9 +347,9 @@ class BackwardRecorder(object):
                     has_l, has_r = ("F", i - 1, 0) in written, ("F", i - 1, 1) in written
                     accumulate = has_l or has_r
                     if accumulate and not has_l:
-                        ops_fill(lib, self.dF[i - 1][:B], 0, self.dF[i - 1][:B].numel())
+                        ops.fill(lib, self.dF[i - 1][:B], 0, self.dF[i - 1][:B].numel())
                     if accumulate and not has_r:
-                        ops_fill(lib, self.dF[i - 1][B:], 0, self.dF[i - 1][B:].numel())
+                        ops.fill(lib, self.dF[i - 1][B:], 0, self.dF[i - 1][B:].numel())
                 if pyr_tr[i]:
                     wgrad(xin, self._fv(self.dF[i]), pyr_name(i), stride=PYR[i - 1][2])
                 if (self.sched.TAIL_SPLIT and i == 2) or i in self.sched.PYR_FLUSH_BEFORE:

@@ -134,8 +134,7 @@ def roofline(lib, eng, stream, reps=20):
     if planes:
         # what the plan runs: the layer from the hi / lo planes of its input (written by context-1's epilogue in the step; split here, outside the
         # timed launches), results as planes only (the plan's post-pass elides the fp32 store of this layer)
-        _, xp = eng._planes_of(x)
-        _, op_ = eng._planes_of(o)
+        xp, op_ = eng.images.planes(x), eng.images.planes(o)
         ops.plane_split(lib, [(x, xp)], eng.dev, keep, stream=sh)
         algo_bytes = 2.0 * 2 * (2 * x.B * x.H * x.W * 128 + 9 * 128 * 128)
 
@@ -162,10 +161,7 @@ def roofline(lib, eng, stream, reps=20):
         bwd_planes = planes and bwd_code == 1 and E.ctx_name(2) in getattr(eng, "banks32t", {})
         if bwd_planes:
             # what the plan runs: dz from its shadow, the mask from the activation's hi plane, the result as a shadow only
-            key = (dz.ptr, dz.B, dz.H, dz.W, dz.C)
-            dzs = eng.shadows.get(key) or ops.Shadow(dz.B, dz.H, dz.W, dz.C, eng.dev)
-            key = (dx.ptr, dx.B, dx.H, dx.W, dx.C)
-            dxs = eng.shadows.get(key) or ops.Shadow(dx.B, dx.H, dx.W, dx.C, eng.dev)
+            dzs, dxs = eng.images.shadow(dz), eng.images.shadow(dx)
             ops.shadow_cast(lib, [(dz, dzs)], eng.dev, keep, stream=sh)
 
         def dgrad():

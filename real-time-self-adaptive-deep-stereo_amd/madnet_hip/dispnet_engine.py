@@ -14,11 +14,14 @@ storages) and the backward plan is derived mechanically from it:
 MAD is not offered for DispNet: the shipped block_config/dispnet_full.json has 5 groups for 6
 predictions, so the reference's own assert fails (Stereo_Online_Adaptation.py:97).
 """
+import ctypes as C
 import os
+
 import torch
 
 from . import ops
-from .engine import Params, _r4, _merge_ranges
+from .base import EngineBase
+from .netdef import _merge_ranges
 from .plan import Recorder
 from .schedule import DispNetSchedule
 
@@ -90,29 +93,10 @@ class Node(object):
         return self.members if self.members else [self]
 
 
-import threading
-_TUNE_LOCK = ops.TUNE_LOCK          # serialises plan recording that scopes a process-wide tuning hook (shared with engine.MadNetEngine.build_plan)
-
-
-class DispNetEngine(object):
+class DispNetEngine(EngineBase):
     def __init__(self, lib, H, W, B=1, device="cuda", weights=None, precision="fp32", schedule=None):
         """schedule: a madnet_hip.schedule.DispNetSchedule (immutable): how this engine's plans are recorded"""
-        self.sched = schedule if schedule is not None else DispNetSchedule()
-        if precision not in ops.PRECISION_CODES:
-            raise ValueError("precision must be one of %s" % sorted(ops.PRECISION_CODES))
-        self.precision = precision
-        self.lib, self.dev = lib, device
-        _td = torch.device(device)
-        if _td.type == "cuda" and hasattr(lib, "ensure_init"):
-            with torch.cuda.device(_td):                  # the per-device set-up of the library, with THIS engine's device current (a process may drive several)
-                lib.ensure_init(torch.cuda.current_device())
-        self.B, self.H0, self.W0 = B, H, W
-        self.Hp = H if H % 64 == 0 else (H // 64 + 1) * 64
-        self.Wp = W if W % 64 == 0 else (W // 64 + 1) * 64
-        self.pt, self.pl = (self.Hp - H) // 2, (self.Wp - W) // 2
-        self.params = Params(dispnet_manifest(), device)
-        if weights is not None:
-            self.params.load(weights)
+        self._init_base(lib, H, W, B, device, dispnet_manifest(), weights, precision, schedule if schedule is not None else DispNetSchedule())
         z = lambda *s: torch.zeros(*s, device=device)
         self.left = z(B, H, W, 3); self.right = z(B, H, W, 3); self.gt = z(B, H, W)
         self.pred = z(B, H, W); self.dpred = z(B, H, W)
@@ -120,39 +104,15 @@ class DispNetEngine(object):
         self.res_loss = self.params.g_loss[self.params.total:self.params.total + 4]; self.res_met = z(4)   # (loss result behind the gradients: one collective carries both)
         self.ops = []
         self.nodes = {}
-        self.wsa = ops.WgradWorkspace(device)
         # bf16 backward: the filter gradients of the 3x3 layers (conv3/1 .. conv6/1, conv4 / 5 / 6 at stride 2, the up-sampling blocks' 3x3 convs and
         # predictions) run on the streaming kernel (mh_wgrad_stream) from bf16 shadows cast per batch; MH_WGRAD_STREAM=0 keeps the tiled kernels
         self.use_stream = precision in ("mixed", "bf16") and os.environ.get("MH_WGRAD_STREAM", "1") != "0"
-        self.shadows = {}
-        self.lo_planes = {}                 # shadow key -> lo plane (split-bf16 layers on mh_conv2d_planes)
         self.banks_f, self.banks_b = {}, {}  # weight name -> fragment bank in the 32x32x16 image (forward: trans 2; input gradient: trans 3)
-        self._fresh = set()                 # shadow keys whose bf16 image is current in the plan being recorded
         self.use_planes = self.sched.USE_PLANES and precision in ("mixed", "bf16") and str(device).startswith(("cuda", "cpu"))
-        ops.check_planes_rule(self.lib)
-        # deterministic test mode (engine.DETERMINISTIC): the bias-gradient atomics accumulate into a fixed-point twin of the flat gradient buffer
-        self.deterministic = self.sched.DETERMINISTIC
-        self._det_bases = []
+        # deterministic test mode: the bias-gradient atomics accumulate into a fixed-point twin of the flat gradient buffer
         if self.deterministic:
-            import ctypes as _C
-            self.det_g = torch.zeros(self.params.total, dtype=torch.int64, device=device)
-            lib.deterministic_add(_C.c_void_p(self.params.g.data_ptr()), self.params.total, _C.c_void_p(self.det_g.data_ptr()))
-            self._det_bases.append(self.params.g.data_ptr())
+            self.det_g, = self._det_twins(self.params.g)
         self._build()
-
-    def close(self):
-        import ctypes as _C
-        for b in self._det_bases:
-            self.lib.deterministic_remove(_C.c_void_p(b))
-        self._det_bases = []
-
-    def __del__(self):
-        try:
-            # (never from inside a stream capture: un-registering synchronises the device, which would invalidate the capture -- call close() explicitly)
-            if self._det_bases and not (torch.cuda.is_available() and torch.cuda.is_current_stream_capturing()):
-                self.close()
-        except Exception:
-            pass
 
     # ---- graph construction -----------------------------------------------------------------------
     def _st(self, H, W, ld, grad=True):
@@ -271,13 +231,6 @@ class DispNetEngine(object):
             return False
         return ops._bwd_precision() == 1 and x.st.ld >= _r8(x.C) and ops.conv2d_planes_bwd_ok(self.lib, x.gview(), w, 1, stride=stride)
 
-    def _shadow_of(self, v):
-        key = (v.ptr, v.B, v.H, v.W, v.C)
-        sh = self.shadows.get(key)
-        if sh is None:
-            sh = self.shadows[key] = ops.Shadow(v.B, v.H, v.W, v.C, self.dev)
-        return key, sh
-
     def _record_banks(self, r, backward):
         """one mh_pack_weights launch at the head of the step: the banks of every layer on the plane kernels (re-packed every step: the weights move)"""
         todo = []
@@ -304,8 +257,8 @@ class DispNetEngine(object):
 
     def record_forward(self, r, backward=True):
         B = self.B
-        self._fresh = set()
-        self._fresh_lo = set()                # tensors whose hi AND lo planes a producer of this plan has written
+        im = self.images
+        im.begin_plan()
         if self.use_planes:
             self._record_banks(r, backward)
         self._grad_zeroed_early = False
@@ -314,7 +267,7 @@ class DispNetEngine(object):
             # beside the forward pass (nothing touches the gradients before the backward pass, whose first op joins the lane)
             r.lane = 1
             try:
-                ops_fill(r, self.params.g, 0, self.params.total)
+                ops.fill(r, self.params.g, 0, self.params.total)
             finally:
                 r.lane = 0
             self._grad_zeroed_early = True
@@ -327,9 +280,7 @@ class DispNetEngine(object):
         if self.sched.PLANES_S2:
             for op2 in self.ops:
                 if op2[0] == "conv" and self._planes_fwd_kind(op2) == 2:
-                    xv2 = op2[1].view()
-                    plane_consumers[(xv2.ptr, xv2.B, xv2.H, xv2.W, xv2.C)] = True
-        vkey = lambda v: (v.ptr, v.B, v.H, v.W, v.C)
+                    plane_consumers[im.key(op2[1].view())] = True
         # activations whose bf16 shadow a later launch of this plan reads: input of a one-plane forward layer, of a streamed filter gradient (3x3, stride 1), leaky mask of
         # a plane input gradient -- their producer writes the shadow
         shadow_readers = set()
@@ -342,7 +293,7 @@ class DispNetEngine(object):
                 streamed = backward and self.use_stream and ops._bwd_precision() == 1 and tuple(w2.shape[:2]) == (3, 3) and stride2 == 1
                 masked = backward and x_grad2 and x2.alpha is not None and self._planes_bwd_ok(op2)
                 if self._planes_fwd_kind(op2) == 1 or streamed or masked:
-                    shadow_readers.add(vkey(x2.view()))
+                    shadow_readers.add(im.key(x2.view()))
         for op in self.ops:
             kind = op[0]
             if kind == "conv":
@@ -351,48 +302,36 @@ class DispNetEngine(object):
                 if kind:
                     # x -> bf16 plane(s) once (the hi plane is the shadow the streamed filter gradient reads: no cast in the backward pass)
                     xv = x.view()
-                    key, sh = self._shadow_of(xv)
                     if kind == 2:
-                        if key not in self.lo_planes:
-                            self.lo_planes[key] = ops.Shadow(xv.B, xv.H, xv.W, xv.C, self.dev)
-                        xp = ops.Planes.__new__(ops.Planes); xp.hi, xp.lo = sh, self.lo_planes[key]
-                        if key not in self._fresh_lo:
+                        xp = im.planes(xv)
+                        if not im.fresh_planes(xv):
                             ops.plane_split(r, [(xv, xp)], self.dev, r.keep)
                     else:
-                        xp = sh
-                        if key not in self._fresh:
-                            ops.shadow_cast(r, [(xv, sh)], self.dev, r.keep)
-                    self._fresh.add(key)
+                        casts = []
+                        xp = im.queue_cast(xv, casts)
+                        ops.shadow_cast(r, casts, self.dev, r.keep)        # (no launch when a producer of this plan wrote the shadow)
+                    im.mark(xv)
                     ov = out.view()
-                    okey = vkey(ov)
+                    okey = im.key(ov)
                     outp = None
                     if ov.C % 8 == 0 and okey in plane_consumers:
-                        _, osh = self._shadow_of(ov)
-                        if okey not in self.lo_planes:
-                            self.lo_planes[okey] = ops.Shadow(ov.B, ov.H, ov.W, ov.C, self.dev)
-                        outp = ops.Planes.__new__(ops.Planes); outp.hi, outp.lo = osh, self.lo_planes[okey]
-                        self._fresh_lo.add(okey); self._fresh.add(okey)
+                        outp = im.planes(ov)
+                        im.mark(ov, lo=True)
                     elif ov.C % 8 == 0 and okey in shadow_readers:
-                        _, outp = self._shadow_of(ov)
-                        self._fresh.add(okey)
+                        outp = im.shadow(ov)
+                        im.mark(ov)
                     ops.conv2d_planes(r, xp, self.W_(wn), self.banks_f[wn][0], self.b_(wn), out=ov, out_planes=outp, alpha=alpha, bf16=(kind == 1), stride=stride)
                     continue
                 ov = out.view()
-                okey = (ov.ptr, ov.B, ov.H, ov.W, ov.C)
-                if okey in shadow_readers and okey not in plane_consumers and ov.C % 8 == 0:
-                    _, osh = self._shadow_of(ov)
-                    ops.conv2d_fwd(r, x.view(), self.W_(wn), self.b_(wn), ov, stride=stride, alpha=alpha, precision=self._fwd_code(wn), shadow=osh)
-                    self._fresh.add(okey)
-                    continue
+                okey = im.key(ov)
+                osh = opl = None
                 if okey in plane_consumers and ov.C % 8 == 0:        # (the fp32 result may be a slice of a concat buffer -- conv1a is a skip connection --: the planes are the view's own)
-                    _, osh = self._shadow_of(ov)
-                    if okey not in self.lo_planes:
-                        self.lo_planes[okey] = ops.Shadow(ov.B, ov.H, ov.W, ov.C, self.dev)
-                    op_ = ops.Planes.__new__(ops.Planes); op_.hi, op_.lo = osh, self.lo_planes[okey]
-                    ops.conv2d_fwd(r, x.view(), self.W_(wn), self.b_(wn), ov, stride=stride, alpha=alpha, precision=self._fwd_code(wn), out_planes=op_)
-                    self._fresh_lo.add(okey); self._fresh.add(okey)
-                    continue
-                ops.conv2d_fwd(r, x.view(), self.W_(wn), self.b_(wn), ov, stride=stride, alpha=alpha, precision=self._fwd_code(wn))
+                    opl = im.planes(ov)
+                    im.mark(ov, lo=True)
+                elif okey in shadow_readers and ov.C % 8 == 0:
+                    osh = im.shadow(ov)
+                    im.mark(ov)
+                ops.conv2d_fwd(r, x.view(), self.W_(wn), self.b_(wn), ov, stride=stride, alpha=alpha, precision=self._fwd_code(wn), shadow=osh, out_planes=opl)
             elif kind == "deconv":
                 _, x, wn, out, alpha = op
                 ops.conv2d_transpose_fwd(r, x.view(), self.W_(wn), self.b_(wn), out.view(), stride=2, alpha=alpha, precision=self._fwd_code(wn))
@@ -434,15 +373,15 @@ class DispNetEngine(object):
 
     def record_backward(self, r, heads=(), early_update=None):
         """heads (offline training): [(prediction node, d loss / d make_disp(node))] -- every _make_disp output carries its own
-        loss term (Train.py:100); each is one more consumer of its node and is injected before the op list is walked."""
-        """early_update = (lr, momentum, grad_scale): see self.sched.EARLY_UPDATE; returns the sorted disjoint [first, end) parameter ranges updated here"""
-        lib, B, P = r, self.B, self.params
+        loss term (Train.py:100); each is one more consumer of its node and is injected before the op list is walked.
+        early_update = (lr, momentum, grad_scale): see self.sched.EARLY_UPDATE; returns the sorted disjoint [first, end) parameter ranges updated here"""
+        lib, B, P, im = r, self.B, self.params, self.images
         upd_fresh, upd_done = [], []
         if getattr(self, "_grad_zeroed_early", False):
             lib.join_lanes_next = 1 << 1            # (the fill issued on lane 1 at the head of the forward pass)
             self._grad_zeroed_early = False
         else:
-            ops_fill(lib, P.g, 0, P.total)
+            ops.fill(lib, P.g, 0, P.total)
         for n in self.nodes.values():
             n.remaining, n.written = n.consumers, False
         for n, _ in heads:
@@ -485,7 +424,7 @@ class DispNetEngine(object):
                     items, casts, todo = [], [], []
                     for xv, dzv, dw, db, stride in pending:
                         if ops.wgrad_stream_ok(xv, dzv, dw, stride, 1) and dw.data_ptr() not in shared_dw:
-                            items.append((self._shadow(xv, casts), self._shadow(dzv, casts), dw, db, 1))
+                            items.append((im.queue_cast(xv, casts), im.queue_cast(dzv, casts), dw, db, 1))
                         else:
                             todo.append((xv, dzv, dw, db, stride))
                     ops.shadow_cast(lib, casts, self.dev, r.keep)
@@ -529,8 +468,8 @@ class DispNetEngine(object):
             sh = None
             if (not xnode.members and xnode.remaining == 0 and len(masks) <= 1 and xnode.name in grad_readers and xnode.C % 8 == 0
                     and (fused is None or fused is xnode)):
-                gk, sh = self._shadow_of(xnode.gview())
-                self._fresh.add(gk)
+                sh = im.shadow(xnode.gview())
+                im.mark(xnode.gview())
             if fused is not None:
                 rng = (fused.c0 - xnode.c0, fused.c0 - xnode.c0 + fused.C)
                 ref = ops.View(xnode.st.t, B, xnode.st.H, xnode.st.W, xnode.C, xnode.st.ld, coff=xnode.c0)
@@ -560,15 +499,12 @@ class DispNetEngine(object):
                         if (not acc or stride == 2) and wn in self.banks_b and self._planes_bwd_ok(op):          # (the stride-2 5x5 form accumulates: conv1a is a skip connection)
                             # dz (and the activation whose sign is the mask) as bf16 planes -- the casts the streamed filter gradient of this very
                             # layer would queue on its side lane anyway -- then the one-plane walk over dz (mh_conv2d_planes_bwd)
-                            kz, dzs = self._shadow_of(dz)
-                            casts = [(dz, dzs)] if kz not in self._fresh else []
-                            ms = None
-                            if ref is not None:
-                                km, ms = self._shadow_of(ref)
-                                if km not in self._fresh:
-                                    casts.append((ref, ms))
-                                self._fresh.add(km)
-                            self._fresh.add(kz)
+                            casts = []
+                            dzs = im.queue_cast(dz, casts)
+                            ms = im.queue_cast(ref, casts) if ref is not None else None
+                            for v in (dz, ref):
+                                if v is not None:
+                                    im.mark(v)
                             ops.shadow_cast(lib, casts, self.dev, r.keep)
                             ops.conv2d_planes_bwd(lib, dzs, w, self.banks_b[wn], dx=dx, dx_shadow=sh, mask_shadow=ms, mask_alpha=ma, mask_range=rng, stride=stride, accumulate=acc)
                             return
@@ -600,20 +536,9 @@ class DispNetEngine(object):
         ops.wgrad_reduce(lib, segs, self.dev, r.keep)
         ops.wgrad_reduce(lib, segs2, self.dev, r.keep, accumulate=True)
         if self.deterministic:
-            import ctypes as _C
             assert not upd_done
-            lib.det_flush(_C.c_void_p(P.g.data_ptr()), _C.c_void_p(self.det_g.data_ptr()), P.total, None)
+            lib.det_flush(C.c_void_p(P.g.data_ptr()), C.c_void_p(self.det_g.data_ptr()), P.total, None)
         return _merge_ranges(upd_done)
-
-    def _shadow(self, v, casts):
-        """the bf16 shadow of View v (allocated on first use) + its cast queued for this batch"""
-        key = (v.ptr, v.B, v.H, v.W, v.C)
-        sh = self.shadows.get(key)
-        if sh is None:
-            sh = self.shadows[key] = ops.Shadow(v.B, v.H, v.W, v.C, self.dev)
-        if key not in self._fresh and not any(c[1] is sh for c in casts):
-            casts.append((v, sh))
-        return sh
 
     def record_update(self, r, lr, momentum=0.9, grad_scale=1.0, done=()):
         """MomentumOptimizer apply on every parameter; done: sorted disjoint [first, end) ranges record_backward(early_update=...) has updated already"""
@@ -624,15 +549,10 @@ class DispNetEngine(object):
                 ops.momentum(r, P.w[a:d0], P.m[a:d0], P.g[a:d0], lr, momentum, grad_scale, n=d0 - a)
             a = max(a, d1)
 
-    def all_vars(self):
-        return [n for n, _ in self.params.manifest]
-
     # ---- offline training (Train.py) -----------------------------------------------------
     def _ensure_train_buffers(self):
-        if getattr(self, "adam_state", None) is None:
+        if self._ensure_adam():
             z = lambda *shape: torch.zeros(*shape, device=self.dev)
-            self.params.v = z(self.params.total)
-            self.adam_state = torch.tensor([0.9, 0.999], device=self.dev)
             self.head_names = ["prediction"] + [u[0] for u in UP_BLOCKS[::-1]]     # disparities[-2], [-3] (up1) ... [-7] (up5)
             self.disp_ms = {k: z(self.B, self.H0, self.W0) for k in self.head_names}
             self.ddisp_ms = {k: z(self.B, self.H0, self.W0) for k in self.head_names}
@@ -656,9 +576,7 @@ class DispNetEngine(object):
             ops.metrics(r, self.pred, self.gt, self.met_ws, self.res_met, 3.0)
             self.record_backward(r, heads=heads)
         if update and part in ("all", "update"):
-            P = self.params
-            ops.adam(r, P.w, P.m, P.v, P.g, self.adam_state, lr, grad_scale=grad_scale, n=P.total)
-            ops.adam_advance(r, self.adam_state)
+            self.record_adam_all(r, lr, grad_scale)
         return r.compile()
 
     def build_plan(self, mode, lr=1e-4, grad_scale=1.0, update=True, part="all", loss_weights=None, max_disp=192.0,
@@ -672,18 +590,14 @@ class DispNetEngine(object):
         # DispNet's filter gradients (few pixels, 256-1024 channels) keep the round-1 pixel-split targets: 3.99 vs 4.08 ms (the split counts are resolved
         # while the plan is recorded and stored in it)
         # (a process-wide hook: recorded under a lock, and what another caller had set is restored -- ADVICE r02)
-        with _TUNE_LOCK:
+        with ops.TUNE_LOCK, ops.precision_scope(self.precision):
             prev = self.lib.tune_wgrad_target_pct(self.WGRAD_TARGET_PCT)
             try:
-                return self._build_plan_scoped(r, mode, lr, grad_scale, update, part, loss_weights, max_disp, optimizer, momentum)
+                if mode == "TRAIN":
+                    return self._build_train_plan(r, lr, grad_scale, update, part, loss_weights, max_disp)
+                return self._build_plan(r, mode, lr, grad_scale, update, part, optimizer, momentum)
             finally:
                 self.lib.tune_wgrad_target_pct(prev)
-
-    def _build_plan_scoped(self, r, mode, lr, grad_scale, update, part, loss_weights, max_disp, optimizer="momentum", momentum=0.9):
-        with ops.precision_scope(self.precision):
-            if mode == "TRAIN":
-                return self._build_train_plan(r, lr, grad_scale, update, part, loss_weights, max_disp)
-            return self._build_plan(r, mode, lr, grad_scale, update, part, optimizer, momentum)
 
     def _build_plan(self, r, mode, lr, grad_scale, update, part, optimizer="momentum", momentum=0.9):
         if optimizer not in ("momentum", "adam"):
@@ -704,20 +618,7 @@ class DispNetEngine(object):
         if mode == "FULL" and do_upd:
             if optimizer == "adam":                       # the live demo's FULL mode (Demo/demo_model.py:148-149,164)
                 self._ensure_train_buffers()
-                P = self.params
-                ops.adam(r, P.w, P.m, P.v, P.g, self.adam_state, lr, grad_scale=grad_scale, n=P.total)
-                ops.adam_advance(r, self.adam_state)
+                self.record_adam_all(r, lr, grad_scale)
             else:
                 self.record_update(r, lr, momentum=momentum, grad_scale=grad_scale, done=done)
         return r.compile()
-
-    def set_inputs(self, left, right, gt=None):
-        self.left.copy_(torch.as_tensor(left, dtype=torch.float32).reshape(self.left.shape))
-        self.right.copy_(torch.as_tensor(right, dtype=torch.float32).reshape(self.right.shape))
-        if gt is not None:
-            self.gt.copy_(torch.as_tensor(gt, dtype=torch.float32).reshape(self.gt.shape))
-
-
-def ops_fill(lib, t, off, count):
-    import ctypes as C
-    lib.fill(C.c_void_p(t.reshape(-1).data_ptr() + 4 * off), count, 0.0, None)

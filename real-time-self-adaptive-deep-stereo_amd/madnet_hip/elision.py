@@ -1,7 +1,8 @@
 """Dead-store elimination over a recorded MADNet plan (post-passes of MadNetEngine.build_plan): fp32 tensors that only bf16-reading kernels consume are not
 stored at all.  A mixin of MadNetEngine: the passes read the engine's tensor lists (E, Cx, dE, dCx), its library handle and its Schedule."""
-import torch      # noqa: F401
+import ctypes as C
 
+from . import _ffi
 from .netdef import LEVELS
 
 
@@ -13,8 +14,6 @@ class ElisionPasses(object):
         maps then exist in bf16 only (15.7 MB less written per 128-channel layer)."""
         if not (self.sched.SHADOW_DGRAD and self.sched.SHADOW_ONLY):
             return 0
-        import ctypes as C
-        from . import _ffi
         ops_ = r.ops
         n = 0
         spans = []
@@ -68,8 +67,6 @@ class ElisionPasses(object):
 
     def _takes_shadows(self, c):
         """mh_conv2d_takes_shadows for a recorded OP_CONV: bit 1 = the launch stages in_shadow, bit 2 = it reads the mask from mask_shadow"""
-        import ctypes as C
-        from . import _ffi
         d = _ffi.ConvDesc(*([c.i[k] for k in range(18)] + [c.i[18], c.f[0], c.f[1], c.i[19], c.i[20], c.i[22]]))
         return self.lib.conv2d_takes_shadows(C.byref(d), C.c_void_p(c.p[0]), C.c_void_p(c.p[1]), C.c_void_p(c.p[6]), C.c_void_p(c.p[3]), C.c_void_p(c.p[4]))
 
@@ -97,7 +94,6 @@ class ElisionPasses(object):
         OVERLAPS the buffer."""
         if not (self.use_planes and self.sched.PLANES_ONLY):
             return 0
-        from . import _ffi
         ops_ = r.ops
         cand = self._standalone_activations()
         n = 0

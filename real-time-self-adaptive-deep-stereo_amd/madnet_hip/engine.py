@@ -13,100 +13,32 @@ Memory layout (all float32, NHWC, resident in HBM for the life of the engine):
     correlation kernel (no tf.concat copies); channel counts are padded to multiples of 4 so all
     row accesses are 16-byte vectors.
 """
+import ctypes as C
 import os
 
-import numpy as np
 import torch
 
 from . import ops
+from .base import EngineBase
+from .params import Params      # noqa: F401  (re-exported: E.Params)
 from .plan import Recorder
 from .schedule import Schedule
 from .elision import ElisionPasses
-from .backward import BackwardRecorder, ops_fill      # noqa: F401
-
-from .netdef import PYR, EST, CTX, LEVELS, FEAT, ALPHA, _r4, pyr_name, est_name, ctx_name, _merge_ranges, madnet_manifest      # noqa: E402,F401  (re-exported: E.LEVELS ...)
-
+from .backward import BackwardRecorder
+from .netdef import PYR, EST, CTX, LEVELS, FEAT, ALPHA, _r4, pyr_name, est_name, ctx_name, _merge_ranges, madnet_manifest      # noqa: F401  (re-exported: E.LEVELS ...)
 
 
-
-
-
-
-
-class Params(object):
-    """Flat fp32 weight / momentum / gradient buffers + name -> (offset, shape) manifest."""
-
-    def __init__(self, manifest, device):
-        self.manifest = manifest
-        self.offset, self.shape = {}, {}
-        off = 0
-        for name, shp in manifest:
-            self.offset[name], self.shape[name] = off, tuple(shp)
-            off += (int(np.prod(shp)) + 3) // 4 * 4          # keep every tensor 16-byte aligned
-        self.total = off
-        self.w = torch.zeros(off, device=device)
-        self.m = torch.zeros(off, device=device)
-        # + 4 floats behind the gradients: the step's loss result lives there, so the shared-model mode all-reduces the
-        # gradients AND the loss that drives the reward / reset logic with ONE collective (adapter.py)
-        self.g_loss = torch.zeros(off + 4, device=device)     # [gradients | loss result (4 floats)]
-        self.g = self.g_loss[:off]
-        self.w0 = None                                         # reset copy (restore target)
-
-    def numel(self, name):
-        return int(np.prod(self.shape[name]))
-
-    def tensor(self, name, which="w"):
-        buf = getattr(self, which)
-        o = self.offset[name]
-        return buf[o:o + self.numel(name)].view(self.shape[name])
-
-    def load(self, weights):
-        """weights: {name: ndarray / tensor} (HWIO); missing names keep their value."""
-        for name, v in weights.items():
-            if name in self.offset:
-                self.tensor(name).copy_(torch.as_tensor(v, dtype=torch.float32).reshape(self.shape[name]))
-
-    def export(self):
-        return {name: self.tensor(name).detach().cpu().numpy().copy() for name, _ in self.manifest}
-
-    def ranges(self, names):
-        """Coalesced (offset, count) ranges covering the given variables."""
-        spans = sorted((self.offset[n], (self.numel(n) + 3) // 4 * 4) for n in set(names))
-        out = []
-        for o, c in spans:
-            if out and out[-1][0] + out[-1][1] == o:
-                out[-1][1] += c
-            else:
-                out.append([o, c])
-        return [(o, c) for o, c in out]
-
-
-class MadNetEngine(ElisionPasses, BackwardRecorder):
+class MadNetEngine(EngineBase, ElisionPasses, BackwardRecorder):
     def __init__(self, lib, H, W, B=1, device="cuda", radius_d=2, stride=1, warping=True, weights=None, precision="fp32", schedule=None):
         """precision: 'fp32' = exact fp32 MFMA (parity path, default) | 'bf16' = bf16 MFMA inputs with fp32
         accumulation in the conv forward / input-gradient kernels (throughput mode; tensors stay fp32).
         schedule: a madnet_hip.schedule.Schedule (immutable; default = the committed bench line's): how this engine's plans are recorded."""
-        self.sched = schedule if schedule is not None else Schedule()
-        if precision not in ops.PRECISION_CODES:
-            raise ValueError("precision must be one of %s" % sorted(ops.PRECISION_CODES))
-        self.precision = precision
+        self._init_base(lib, H, W, B, device, madnet_manifest(radius_d, stride), weights, precision, schedule if schedule is not None else Schedule())
         # warping=False (MadNet.py:282-285,301-304,...): the right features enter the cost volume un-warped; the upsampled
         # disparity still joins the estimator input
         self.warping = bool(warping)
-        self.lib, self.dev = lib, device
-        _td = torch.device(device)
-        if _td.type == "cuda" and hasattr(lib, "ensure_init"):
-            with torch.cuda.device(_td):                  # the per-device set-up of the library, with THIS engine's device current (a process may drive several)
-                lib.ensure_init(torch.cuda.current_device())
-        self.B, self.H0, self.W0 = B, H, W
         self.md, self.cstride = radius_d, stride
         self.D = 2 * radius_d // stride + 1
-        self.Hp = H if H % 64 == 0 else (H // 64 + 1) * 64          # preprocessing.pad_image(., 64)
-        self.Wp = W if W % 64 == 0 else (W // 64 + 1) * 64
-        self.pt, self.pl = (self.Hp - H) // 2, (self.Wp - W) // 2
-        self.params = Params(madnet_manifest(radius_d, stride), device)
-        if weights is not None:
-            self.params.load(weights)
         self._alloc()
         self._plans = {}
         self._zeros_needed = []
@@ -130,22 +62,17 @@ class MadNetEngine(ElisionPasses, BackwardRecorder):
         self.bank_min_n = 32
         self.banks = {}
         self.banks_d = {}
-        self.wsa = ops.WgradWorkspace(device)
         # bf16 backward: the filter gradients of the stride-1 3x3 layers run on the streaming kernel (mh_wgrad_stream: one launch per batch,
         # operands from bf16 shadows of the activations / gradient maps); MH_WGRAD_STREAM=0 keeps the tiled kernels
         self.use_stream = precision in ("mixed", "bf16") and os.environ.get("MH_WGRAD_STREAM", "1") != "0"
         self.stream_min_pix = 0
-        self.shadows = {}                   # (data pointer, B, H, W, C) -> ops.Shadow, allocated once per engine
-        # ... written by the epilogue of the kernel that produces the tensor (mh_conv2d_sh) wherever a conv kernel is the producer; the rest
+        # the bf16 shadows (self.images) are written by the epilogue of the kernel that produces the tensor (mh_conv2d_sh) wherever a conv kernel is the producer; the rest
         # (cost-volume buffers, heads, the top pyramid gradient) go through one mh_shadow_cast per batch.  fuse_shadows = False: cast everything
         self.fuse_shadows = True
-        self._fresh = set()                 # shadows a producer wrote in the plan being recorded
         self._stream_train = set()          # trainable variables of that plan
         self.use_planes = self.use_bank and precision == "mixed" and self.sched.USE_PLANES
         self.banks32 = {}                   # layer -> fragment bank in the 32x32x16 image (mh_pack_weights trans = 2)
         self.banks32t = {}                  # layer -> the input gradient's one-plane bank in that image (trans = 3)
-        self.planes = {}                    # (data pointer, B, H, W, C) -> ops.Planes (hi = the entry of self.shadows)
-        self._fresh_planes = set()          # planes (hi AND lo) a producer wrote in the plan being recorded
 
     # ---------------------------------------------------------------------------------------
     def _buf(self, *shape):
@@ -179,16 +106,8 @@ class MadNetEngine(ElisionPasses, BackwardRecorder):
                 off += n
             else:
                 self.dF[i] = z(B2, hh, ww, co)
-        self.deterministic = self.sched.DETERMINISTIC
-        ops.check_planes_rule(self.lib)
-        self._det_bases = []
         if self.deterministic:
-            self.det_g = torch.zeros(self.params.total, dtype=torch.int64, device=self.dev)
-            self.det_dF = torch.zeros(self.dF_levels.numel(), dtype=torch.int64, device=self.dev)
-            import ctypes as _C
-            for base, n, twin in ((self.params.g, self.params.total, self.det_g), (self.dF_levels, self.dF_levels.numel(), self.det_dF)):
-                self.lib.deterministic_add(_C.c_void_p(base.data_ptr()), n, _C.c_void_p(twin.data_ptr()))
-                self._det_bases.append(base.data_ptr())
+            self.det_g, self.det_dF = self._det_twins(self.params.g, self.dF_levels)
         self.Rw, self.dRw, self.dsi, self.ddsi, self.E, self.dE, self.V, self.dV, self.u, self.du = ({} for _ in range(10))
         self.dsi_ld = {}
         for k in LEVELS:
@@ -350,31 +269,18 @@ class MadNetEngine(ElisionPasses, BackwardRecorder):
         """does mh_conv2d_planes_bwd have an instance for the input gradient of a stride-1 3x3 layer K -> N?"""
         if not (self.use_planes and self.sched.PLANES_DGRAD):
             return False
-        import ctypes as C
         d = ops.conv_desc(1, 8, 8, 8, 8, K, N, 3, 3, 1, 1, 1, 1, 0, 0, K, 0, precision=1)
         return self.lib.conv2d_planes_bwd_ok(C.byref(d)) == 1
 
     def _bank_of(self, trans):
         return {0: self.banks, 1: self.banks_d, 2: self.banks32, 3: self.banks32t}[trans]
 
-    def _planes_of(self, v):
-        """the Planes object of View v (allocated on first use; its hi plane is v's Shadow)"""
-        key = (v.ptr, v.B, v.H, v.W, v.C)
-        pl = self.planes.get(key)
-        if pl is None:
-            sh = self.shadows.get(key)
-            if sh is None:
-                sh = self.shadows[key] = ops.Shadow(v.B, v.H, v.W, v.C, self.dev)
-            pl = self.planes[key] = ops.Planes(sh, self.dev)
-        return key, pl
-
     def _in_planes(self, lib, v, r):
         """planes of an input View: as a producer of this plan left them, else split here (one launch; tensors no plane-writing kernel produces)"""
-        key, pl = self._planes_of(v)
-        if key not in self._fresh_planes:
+        pl = self.images.planes(v)
+        if not self.images.fresh_planes(v):
             ops.plane_split(lib, [(v, pl)], self.dev, r.keep)
-            self._fresh_planes.add(key)
-            self._fresh.add(key)                # the hi plane is the tensor's bf16 shadow: no cast in the backward pass
+            self.images.mark(v, lo=True)        # the hi plane is the tensor's bf16 shadow: no cast in the backward pass
         return pl
 
     def _conv_fwd(self, lib, r, x, base, o, stride=1, dil=1, alpha=ALPHA, precision=None, shadow_consumer=None):
@@ -382,18 +288,14 @@ class MadNetEngine(ElisionPasses, BackwardRecorder):
         wb32 = self.banks32.get(base)              # (stride 2: only the layers _bank_plan gave a 32x32x16 bank -- Schedule.PLANES_S2_FWD)
         if wb32 is not None:
             xp = self._in_planes(lib, x, r)
-            key, op_ = self._planes_of(o)
-            ops.conv2d_planes(lib, xp, self.W_(base), wb32, self.b_(base), out=o, out_planes=op_, dil=dil, alpha=alpha, stride=stride)
-            self._fresh_planes.add(key)
-            self._fresh.add(key)
+            ops.conv2d_planes(lib, xp, self.W_(base), wb32, self.b_(base), out=o, out_planes=self.images.planes(o), dil=dil, alpha=alpha, stride=stride)
+            self.images.mark(o, lo=True)
             return
         if shadow_consumer and shadow_consumer in self.banks32 and self.sched.FUSE_SPLITS:
             # the consumer runs from planes: this layer's epilogue writes them (mh_conv2d_sh4) instead of a split launch in front of the consumer
-            key, op_ = self._planes_of(o)
             ops.conv2d_fwd(lib, x, self.W_(base), self.b_(base), o, stride=stride, dil=dil, alpha=alpha, wb=self.Wb_(base), precision=precision,
-                           out_planes=op_)
-            self._fresh_planes.add(key)
-            self._fresh.add(key)
+                           out_planes=self.images.planes(o))
+            self.images.mark(o, lo=True)
             return
         sh = self._out_shadow(o, shadow_consumer) if shadow_consumer else None
         ops.conv2d_fwd(lib, x, self.W_(base), self.b_(base), o, stride=stride, dil=dil, alpha=alpha,
@@ -405,7 +307,7 @@ class MadNetEngine(ElisionPasses, BackwardRecorder):
         self._x0_pending = False
         head2_fused = False
         pending_head = None
-        self._fresh_planes = set()
+        self.images.begin_plan()
         self._stamp(lib, "start")
         if self.use_bank:
             plan = self._bank_plan()
@@ -464,13 +366,13 @@ class MadNetEngine(ElisionPasses, BackwardRecorder):
                 xin = ops.View(self.dsi[k], B, h, w, c + self.D + 1, ld)
                 pl = None
                 if self.sched.FUSE_SPLITS and self.use_planes and self.cstride == 1:
-                    key, pl_ = self._planes_of(xin)
+                    pl_ = self.images.planes(xin)
                     if est_name(k, 1) in self.banks32:
                         pl = pl_                                  # hi + lo: the estimator's first layer runs from planes
-                        self._fresh_planes.add(key); self._fresh.add(key)
+                        self.images.mark(xin, lo=True)
                     elif (est_name(k, 1) + "/weights") in self._stream_train and self.use_stream and self.partial_wgrad and ops._bwd_precision() == 1:
                         pl = pl_.hi                               # hi only: the shadow its streamed filter gradient reads (no cast in the backward pass)
-                        self._fresh.add(key)
+                        self.images.mark(xin)
                 if head is not None:
                     # ... and the disparity head of level k + 1 (recorded nowhere else: see below)
                     hx, hname = head
@@ -526,9 +428,8 @@ class MadNetEngine(ElisionPasses, BackwardRecorder):
         if concat_split:
             # the planes of tf.concat([left features, V2]) straight from the two sources: the first layer takes the planes, its streamed filter gradient
             # the hi plane, its input gradient has no mask -- nothing reads an fp32 copy of the concatenation
-            key, pl = self._planes_of(cin)
-            ops.plane_split(lib, [((self._half(self.F[4], False), self._fv(self.V[2])), pl)], self.dev, r.keep)
-            self._fresh_planes.add(key); self._fresh.add(key)
+            ops.plane_split(lib, [((self._half(self.F[4], False), self._fv(self.V[2])), self.images.planes(cin))], self.dev, r.keep)
+            self.images.mark(cin, lo=True)
         else:
             ops.copy_channels(lib, self._half(self.F[4], False), cin.slice(0, c))
             if not head2_fused:
@@ -548,17 +449,6 @@ class MadNetEngine(ElisionPasses, BackwardRecorder):
         ops.resize_fwd(lib, self.final, self.pred, self.Hp, self.Wp, self.pt, self.pl, mul=-20.0, mode=2)
         self._stamp(lib, "forward_end")
 
-    def _shadow(self, v, casts):
-        """the bf16 shadow of View v (allocated on first use); queues its cast unless the producing kernel wrote it (self._fresh) or this
-        batch already queued it"""
-        key = (v.ptr, v.B, v.H, v.W, v.C)
-        sh = self.shadows.get(key)
-        if sh is None:
-            sh = self.shadows[key] = ops.Shadow(v.B, v.H, v.W, v.C, self.dev)
-        if key not in self._fresh and not any(c[1] is sh for c in casts):
-            casts.append((v, sh))
-        return sh
-
     def _out_shadow(self, v, consumer):
         """Shadow the PRODUCER of View v should write in its epilogue (mh_conv2d_sh), or None: only when the filter gradient of the layer
         `consumer` (a variable base name) is streamed in the plan being recorded."""
@@ -566,21 +456,13 @@ class MadNetEngine(ElisionPasses, BackwardRecorder):
             return None
         if (consumer + "/weights") not in self._stream_train or v.npix < self.stream_min_pix:
             return None
-        key = (v.ptr, v.B, v.H, v.W, v.C)
-        sh = self.shadows.get(key)
-        if sh is None:
-            sh = self.shadows[key] = ops.Shadow(v.B, v.H, v.W, v.C, self.dev)
-        self._fresh.add(key)
-        return sh
+        self.images.mark(v)
+        return self.images.shadow(v)
 
     def _fresh_shadow(self, v):
         """the bf16 shadow of View v if a producer recorded earlier in this plan wrote it (the patch-staged input-gradient kernel then stages
         it instead of converting v), else None"""
-        if not (self.sched.SHADOW_DGRAD and ops._bwd_precision() == 1):
-            return None
-        key = (v.ptr, v.B, v.H, v.W, v.C)
-        return self.shadows.get(key) if key in self._fresh else None
-
+        return self.images.fresh(v) if (self.sched.SHADOW_DGRAD and ops._bwd_precision() == 1) else None
 
     def _front_fused(self):
         return self.fuse_front and self.warping and self.cstride == 1 and self.D <= 9
@@ -593,7 +475,6 @@ class MadNetEngine(ElisionPasses, BackwardRecorder):
         return self.lib.level_front_head_ok(x.H, x.W, h, w, c, x.C, self.md) == 1
 
     def _conv_acc(self, lib, x, base, out, rate):
-        import ctypes as C
         w = self.W_(base)
         kh, kw, cin, cout = w.shape
         Ho, Wo, pt, pl = ops.conv_geometry(x.H, x.W, kh, kw, 1, rate)
@@ -648,25 +529,9 @@ class MadNetEngine(ElisionPasses, BackwardRecorder):
         """deterministic mode: t (a contiguous slice of base_all) += its fixed-point twin; recorded where the next reader of t follows"""
         if not self.deterministic:
             return
-        import ctypes as _C
         off = (t.data_ptr() - base_all.data_ptr()) // 4
         assert t.is_contiguous() and 0 <= off and off + t.numel() <= base_all.numel()
-        lib.det_flush(_C.c_void_p(t.data_ptr()), _C.c_void_p(twin_all.data_ptr() + 8 * off), t.numel(), None)
-
-    def close(self):
-        """deterministic mode: un-register this engine's ranges (the table holds 8 per process)"""
-        import ctypes as _C
-        for b in self._det_bases:
-            self.lib.deterministic_remove(_C.c_void_p(b))
-        self._det_bases = []
-
-    def __del__(self):
-        try:
-            # (never from inside a stream capture: un-registering synchronises the device, which would invalidate the capture -- call close() explicitly)
-            if self._det_bases and not (torch.cuda.is_available() and torch.cuda.is_current_stream_capturing()):
-                self.close()
-        except Exception:
-            pass
+        lib.det_flush(C.c_void_p(t.data_ptr()), C.c_void_p(twin_all.data_ptr() + 8 * off), t.numel(), None)
 
     def record_update(self, r, train_vars, lr, momentum=0.9, grad_scale=1.0, done=()):
         """MomentumOptimizer apply on the (coalesced) ranges of train_vars; done: sorted disjoint [first, end) ranges that
@@ -701,10 +566,8 @@ class MadNetEngine(ElisionPasses, BackwardRecorder):
     def _ensure_train_buffers(self):
         """Buffers only the offline-training plan needs: second Adam moment, beta powers, one gradient map and one result
         slot per predicted scale."""
-        if getattr(self, "adam_state", None) is None:
-            z = lambda *shape: torch.zeros(*shape, device=self.dev)
-            self.params.v = z(self.params.total)
-            self.adam_state = torch.tensor([0.9, 0.999], device=self.dev)
+        if self._ensure_adam():
+            z = self._buf
             self.ddisp_ms = {k: z(self.B, self.H0, self.W0) for k in LEVELS}
             self.res_loss_ms = z(6, 4)                 # rows: final, level 2 (context), 3, 4, 5, 6 = disparities[-1], [-2], ...
             self.sup_ws = z(self.lib.proxy_ws_floats(self.B, self.H0, self.W0))
@@ -712,9 +575,6 @@ class MadNetEngine(ElisionPasses, BackwardRecorder):
     # =========================================================================================
     # compiled step plans
     # =========================================================================================
-    def all_vars(self):
-        return [n for n, _ in self.params.manifest]
-
     def pyramid_range(self):
         """(offset, count) of the pyramid's variables in the flat buffers: they lead the layout (madnet_manifest), the estimators and the
         context network follow -- the two pieces of the shared-model all-reduce."""
@@ -741,7 +601,6 @@ class MadNetEngine(ElisionPasses, BackwardRecorder):
         if inputs is not None and part != "update":
             ops.fetch_inputs(r, inputs.ptr, [self.left, self.right, self.gt, self.proxy])
         self.wsa.reset()
-        self._fresh = set()
         self.stamp_labels = []
         if mode in ("FULL", "TRAIN"):
             self._stream_train = set(self.all_vars())
@@ -866,7 +725,7 @@ class MadNetEngine(ElisionPasses, BackwardRecorder):
                     raise NotImplementedError("reprojectionScale != 1 is implemented for the reprojection loss (the online script)")
                 ops.resize_image(r, self.left, self.left_s)           # inputs_modules (Stereo_Online_Adaptation.py:91-95)
                 ops.resize_image(r, self.right, self.right_s)
-            for lv, bv in blocks:
+            for nb, (lv, bv) in enumerate(blocks):
                 if do_grad:
                     # loss of the block's prediction: reprojection (Stereo_Online_Adaptation.py:98-107) or, continual
                     # variant, proxy-label mean_l1 with weight 0.1 (Stereo_Continual_Adaptation.py:100-112)
@@ -885,7 +744,7 @@ class MadNetEngine(ElisionPasses, BackwardRecorder):
                     # the block's gradient ranges + the loss tail (behind the gradient buffer) as ONE RCCL group between the block's backward pass and its update
                     P = self.params
                     rng = [(P.g_loss, o, c) for o, c in P.ranges(bv)]
-                    if lv is blocks[0][0]:                          # (the loss result travels once per step: with the first block's gradients)
+                    if nb == 0:                                     # (the loss result travels once per step: with the first block's gradients)
                         if rng and rng[-1][1] + rng[-1][2] == P.total:
                             rng[-1] = (P.g_loss, rng[-1][1], rng[-1][2] + 4)
                         else:
@@ -905,12 +764,3 @@ class MadNetEngine(ElisionPasses, BackwardRecorder):
         self._elide_fp32_gradient_maps(r)
         self._elide_fp32_activations(r)
         return r.compile_parts() if part == "grad_split" else r.compile()
-
-    # convenience: eager single forward -------------------------------------------------------
-    def set_inputs(self, left, right, gt=None, proxy=None):
-        self.left.copy_(torch.as_tensor(left, dtype=torch.float32).reshape(self.left.shape))
-        self.right.copy_(torch.as_tensor(right, dtype=torch.float32).reshape(self.right.shape))
-        if gt is not None:
-            self.gt.copy_(torch.as_tensor(gt, dtype=torch.float32).reshape(self.gt.shape))
-        if proxy is not None:
-            self.proxy.copy_(torch.as_tensor(proxy, dtype=torch.float32).reshape(self.proxy.shape))

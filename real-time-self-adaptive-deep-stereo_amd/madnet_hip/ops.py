@@ -333,15 +333,21 @@ class Planes(object):
     conv2d_planes (csrc/conv_planes.hip).  `hi` is an ordinary Shadow -- the one the streamed filter gradient and the input gradients read."""
     __slots__ = ("hi", "lo")
 
-    def __init__(self, hi, device):
+    def __init__(self, hi, lo=None):
+        """lo: the lo plane's Shadow | None = hi only (the one-plane forms) | a device: the lo plane is allocated there"""
         self.hi = hi
-        self.lo = Shadow(hi.B, hi.H, hi.W, hi.C, device)
+        self.lo = lo if (lo is None or isinstance(lo, Shadow)) else Shadow(hi.B, hi.H, hi.W, hi.C, lo)
 
     B = property(lambda self: self.hi.B)
     H = property(lambda self: self.hi.H)
     W = property(lambda self: self.hi.W)
     C = property(lambda self: self.hi.C)
     ld = property(lambda self: self.hi.ld)
+
+
+def as_planes(x):
+    """the one handle of the plane wrappers: a Planes as it is, a bare Shadow as the hi-only Planes on it"""
+    return x if isinstance(x, Planes) else Planes(x)
 
 
 def conv2d_planes_ok(qlib, x, w, dil=1, bf16=False, stride=1):
@@ -366,9 +372,7 @@ def conv2d_planes(lib, xp, w, wb32, b, out=None, out_planes=None, dil=1, alpha=1
     bf16: plain bf16 (one MFMA per product) from the hi plane alone -- xp may be a bare Shadow, wb32 the ONE-plane bank (pack planes = 1)."""
     kh, kw, cin, cout = w.shape
     assert xp.C == cin and ((kh, kw) == (3, 3) if stride == 1 else (stride == 2 and kh == kw and dil == 1 and xp.H % 2 == 0 and xp.W % 2 == 0))
-    if bf16:
-        xhi = xp.hi if isinstance(xp, Planes) else xp
-        xp = _HiOnly(xhi)
+    xp = Planes(as_planes(xp).hi) if bf16 else as_planes(xp)
     Ho, Wo = xp.H // stride, xp.W // stride
     pad = dil if stride == 1 else (kh - 2) // 2                  # TF 'SAME': stride 2 on even sizes pads (k - 2) // 2 in front (SURVEY A.1)
     d = conv_desc(xp.B, xp.H, xp.W, Ho, Wo, cin, cout, kh, kw, stride, dil, pad, pad, 0, 0, 0, (out.ld if out is not None else 0), alpha=alpha,
@@ -376,28 +380,13 @@ def conv2d_planes(lib, xp, w, wb32, b, out=None, out_planes=None, dil=1, alpha=1
     ohi = olo = None
     opld = 0
     if out_planes is not None:
-        hi = out_planes.hi if isinstance(out_planes, Planes) else out_planes
-        lo = out_planes.lo if isinstance(out_planes, Planes) else None
+        hi, lo = as_planes(out_planes).hi, as_planes(out_planes).lo
         assert (hi.B, hi.H, hi.W, hi.C) == (xp.B, Ho, Wo, cout)
         ohi, olo, opld = C.c_void_p(hi.ptr), (C.c_void_p(lo.ptr) if lo is not None else None), hi.ld
     if out is not None:
         assert (out.B, out.H, out.W, out.C) == (xp.B, Ho, Wo, cout)
     lib.conv2d_planes(C.byref(d), C.c_void_p(xp.hi.ptr), (C.c_void_p(xp.lo.ptr) if xp.lo is not None else None), xp.ld, _p(wb32), _p(b), _p(out), ohi, olo, opld,
                       _p(stream))
-
-
-class _HiOnly(object):
-    """a Planes-shaped handle on a bare Shadow (the one-plane forms)"""
-    __slots__ = ("hi", "lo")
-
-    def __init__(self, hi):
-        self.hi, self.lo = hi, None
-
-    B = property(lambda self: self.hi.B)
-    H = property(lambda self: self.hi.H)
-    W = property(lambda self: self.hi.W)
-    C = property(lambda self: self.hi.C)
-    ld = property(lambda self: self.hi.ld)
 
 
 def conv2d_planes_bwd_ok(qlib, dx, w, dil=1, stride=1):
@@ -440,8 +429,7 @@ def plane_split(lib, pairs, device, keep, stream=None):
     arr = (_ffi.PlaneSeg * len(pairs))()
     blk = 0
     for i, (src, dst) in enumerate(pairs):
-        hi = dst.hi if isinstance(dst, Planes) else dst
-        lo = dst.lo if isinstance(dst, Planes) else None
+        hi, lo = as_planes(dst).hi, as_planes(dst).lo
         src2 = None
         if isinstance(src, (tuple, list)):      # (View a, View b): the planes of tf.concat([a, b], -1)
             src, src2 = src
@@ -621,8 +609,7 @@ def level_front_fwd(lib, Vc, mul, L, R, out, Rw, u, max_disp, coff, zero_tail=Tr
         lib.level_front_fwd(_p(Vc), Vc.shape[1], Vc.shape[2], mul, _p(L), L.ld, _p(R), R.ld, _p(out), out.ld, coff, _p(Rw), Rw.ld, _p(u),
                             L.B, L.H, L.W, L.C, max_disp, int(zero_tail), _p(stream))
         return
-    hi = planes.hi if isinstance(planes, Planes) else planes
-    lo = planes.lo if isinstance(planes, Planes) else None
+    hi, lo = as_planes(planes).hi, as_planes(planes).lo
     assert (hi.B, hi.H, hi.W) == (L.B, L.H, L.W) and hi.C == coff + 2 * max_disp + 2 and hi.ld >= hi.C
     lib.level_front_fwd_planes(_p(Vc), Vc.shape[1], Vc.shape[2], mul, _p(L), L.ld, _p(R), R.ld, _p(out), out.ld, coff, _p(Rw), Rw.ld, _p(u),
                                L.B, L.H, L.W, L.C, max_disp, int(zero_tail), C.c_void_p(hi.ptr), (C.c_void_p(lo.ptr) if lo is not None else None), hi.ld, _p(stream))
@@ -633,8 +620,7 @@ def level_front_head_fwd(lib, X, hw, hb, Vc, mul, L, R, out, Rw, u, max_disp, co
     X: View [B,Hc,Wc,K]; hw: the head's [3,3,K,1] weights; hb: its bias tensor or None; Vc: [B,Hc,Wc] tensor (output)."""
     hi = lo = None
     if planes is not None:
-        hi = planes.hi if isinstance(planes, Planes) else planes
-        lo = planes.lo if isinstance(planes, Planes) else None
+        hi, lo = as_planes(planes).hi, as_planes(planes).lo
         assert (hi.B, hi.H, hi.W) == (L.B, L.H, L.W) and hi.C == coff + 2 * max_disp + 2 and hi.ld >= hi.C
     assert (X.B, X.H, X.W) == (L.B, Vc.shape[1], Vc.shape[2]) and tuple(hw.shape) == (3, 3, X.C, 1)
     lib.level_front_head_fwd(_p(X), X.ld, X.C, _p(hw), _p(hb), _p(Vc), Vc.shape[1], Vc.shape[2], mul, _p(L), L.ld, _p(R), R.ld, _p(out), out.ld, coff, _p(Rw), Rw.ld,
@@ -795,6 +781,11 @@ def metrics(lib, disp, gt, ws, result, pixel_th=3.0, stream=None):
 
 def momentum(lib, var, accum, grad, lr, mom=0.9, grad_scale=1.0, n=None, stream=None):
     lib.momentum(_p(var), _p(accum), _p(grad), n if n is not None else var.numel(), lr, mom, grad_scale, _p(stream))
+
+
+def fill(lib, t, off, count, stream=None):
+    """zero fill of t.flatten()[off:off + count]"""
+    lib.fill(C.c_void_p(t.reshape(-1).data_ptr() + 4 * off), count, 0.0, _p(stream))
 
 
 def copy_channels(lib, src, dst, nch=None, scale=1.0, accumulate=False, stream=None):
