@@ -970,15 +970,7 @@ int launch_one(ConvArgs& a, hipStream_t s) {
     constexpr size_t lds = KG * tiles + 1536;          // + tap_dy / tap_dx / tap_id [64] and row_m [128]
     static_assert(lds <= 160 * 1024, "tiles do not fit the 160 KiB LDS");
     static std::atomic<uint64_t> attr_done{0};       // LDS > 64 KiB needs the opt-in once per instantiation
-    const uint64_t attr_dev = mh_device_bit();
-    if (!(attr_done.load(std::memory_order_relaxed) & attr_dev)) {
-        if (lds > 64 * 1024) {
-            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_igemm_kernel<WM, WN, MT, NT, KT, DGRAD, VEC, UNI, BF16, KG, X3, RAG>),
-                                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-            if (e != hipSuccess) { mh_set_error("conv: hipFuncSetAttribute(%d B LDS): %s", (int)lds, hipGetErrorString(e)); return (int)e; }
-        }
-        attr_done.fetch_or(attr_dev);
-    }
+    if (int rc = mh_lds_optin(attr_done, reinterpret_cast<const void*>(&conv_igemm_kernel<WM, WN, MT, NT, KT, DGRAD, VEC, UNI, BF16, KG, X3, RAG>), (int)lds, "conv")) return rc;
     if (a.M < 0) return 0;               // mh_init(): attribute set-up only
     a.mtiles = mh_cdiv(a.M, BM);
     a.ntiles = mh_cdiv(a.N, BN);
@@ -1160,10 +1152,17 @@ int mh_conv_init() {
     return rc ? rc : conv_dispatch(a, nullptr);
 }
 
-struct HeadOuts { float* out2; int out2_ld; float* out3; int out3_ld; const void* in_shadow; const void* mask_shadow = nullptr; int flags = 0; int query = 0; void* out_lo = nullptr; };
+// what the entry points after mh_conv2d added to its arguments (all optional)
+struct HeadOuts {
+    const char* entry = "mh_conv2d";                 // the exported name, for the messages of the checks below
+    float* out2 = nullptr; int out2_ld = 0; float* out3 = nullptr; int out3_ld = 0;      // mh_conv2d_head
+    void* out_shadow = nullptr; void* out_lo = nullptr;                                  // bf16 shadow of the result (_sh*), its lo plane (_sh4)
+    const void* in_shadow = nullptr; const void* mask_shadow = nullptr; int flags = 0;   // _sh2 / _sh3
+    int query = 0;                                                                       // mh_conv2d_takes_shadows: answer, launch nothing
+};
 int mh_plane_split_one(const float* src, int src_ld, int C, void* hi, void* lo, int dst_ld, int64_t npix, hipStream_t s);      // conv_planes.hip
-static int conv_entry(const mh_conv_desc* d, const float* in, const float* w, const float* wt, const void* wb, const float* bias,
-                      float* out, const float* mask_ref, void* stream, void* out_shadow = nullptr, const HeadOuts* head = nullptr);
+static int conv_entry(const mh_conv_desc* d, const float* in, const float* w, const void* wb, const float* bias,
+                      float* out, const float* mask_ref, void* stream, const HeadOuts& h = HeadOuts());
 int mh_shadow_cast_one(const float* src, int src_ld, int C, void* dst, int dst_ld, int64_t npix, hipStream_t s);      // wgrad_stream.hip
 #ifdef MH_PHASE_TIMING
 static unsigned long long* g_conv_dbg = nullptr;
@@ -1171,57 +1170,103 @@ extern "C" int mh_tune_conv_dbg(void* buf) { g_conv_dbg = (unsigned long long*)b
 #endif
 extern "C" int mh_conv2d(const mh_conv_desc* d, const float* in, const float* w, const float* bias,
                          float* out, const float* mask_ref, void* stream) {
-    return conv_entry(d, in, w, nullptr, nullptr, bias, out, mask_ref, stream);
+    return conv_entry(d, in, w, nullptr, bias, out, mask_ref, stream);
 }
 extern "C" int mh_conv2d_wb(const mh_conv_desc* d, const float* in, const float* w, const void* wb, const float* bias,
                             float* out, const float* mask_ref, void* stream) {
-    return conv_entry(d, in, w, nullptr, wb, bias, out, mask_ref, stream);
+    return conv_entry(d, in, w, wb, bias, out, mask_ref, stream);
 }
 extern "C" int mh_conv2d_sh(const mh_conv_desc* d, const float* in, const float* w, const void* wb, const float* bias,
                             float* out, const float* mask_ref, void* out_shadow, void* stream) {
-    MH_REQUIRE(!out_shadow || (((uintptr_t)out_shadow) & 15u) == 0, MH_ERR_ALIGN, "mh_conv2d_sh: out_shadow must be 16-byte aligned");
-    return conv_entry(d, in, w, nullptr, wb, bias, out, mask_ref, stream, out_shadow);
+    HeadOuts h;
+    h.entry = "mh_conv2d_sh"; h.out_shadow = out_shadow;
+    return conv_entry(d, in, w, wb, bias, out, mask_ref, stream, h);
 }
 extern "C" int mh_conv2d_sh2(const mh_conv_desc* d, const float* in, const void* in_shadow, const float* w, const void* wb, const float* bias,
                              float* out, const float* mask_ref, void* out_shadow, void* stream) {
-    MH_REQUIRE(!out_shadow || (((uintptr_t)out_shadow) & 15u) == 0, MH_ERR_ALIGN, "mh_conv2d_sh2: out_shadow must be 16-byte aligned");
-    MH_REQUIRE(!in_shadow || (((uintptr_t)in_shadow) & 15u) == 0, MH_ERR_ALIGN, "mh_conv2d_sh2: in_shadow must be 16-byte aligned");
-    const HeadOuts h{nullptr, 0, nullptr, 0, in_shadow};
-    return conv_entry(d, in, w, nullptr, wb, bias, out, mask_ref, stream, out_shadow, &h);
+    HeadOuts h;
+    h.entry = "mh_conv2d_sh2"; h.out_shadow = out_shadow; h.in_shadow = in_shadow;
+    return conv_entry(d, in, w, wb, bias, out, mask_ref, stream, h);
 }
 extern "C" int mh_conv2d_sh3(const mh_conv_desc* d, const float* in, const void* in_shadow, const float* w, const void* wb, const float* bias,
                              float* out, const float* mask_ref, const void* mask_shadow, void* out_shadow, int32_t flags, void* stream) {
-    MH_REQUIRE(!out_shadow || (((uintptr_t)out_shadow) & 15u) == 0, MH_ERR_ALIGN, "mh_conv2d_sh3: out_shadow must be 16-byte aligned");
-    MH_REQUIRE(!in_shadow || (((uintptr_t)in_shadow) & 15u) == 0, MH_ERR_ALIGN, "mh_conv2d_sh3: in_shadow must be 16-byte aligned");
-    MH_REQUIRE(!mask_shadow || (((uintptr_t)mask_shadow) & 15u) == 0, MH_ERR_ALIGN, "mh_conv2d_sh3: mask_shadow must be 16-byte aligned");
-    MH_REQUIRE(!(flags & 1) || (out_shadow && !d->accumulate), MH_ERR_ARG, "mh_conv2d_sh3: MH_CONV_SHADOW_ONLY needs out_shadow and no accumulation");
-    HeadOuts h{nullptr, 0, nullptr, 0, in_shadow};
-    h.mask_shadow = mask_shadow; h.flags = flags;
-    return conv_entry(d, in, w, nullptr, wb, bias, out, mask_ref, stream, out_shadow, &h);
+    HeadOuts h;
+    h.entry = "mh_conv2d_sh3"; h.out_shadow = out_shadow; h.in_shadow = in_shadow; h.mask_shadow = mask_shadow; h.flags = flags;
+    return conv_entry(d, in, w, wb, bias, out, mask_ref, stream, h);
 }
 extern "C" int mh_conv2d_sh4(const mh_conv_desc* d, const float* in, const float* w, const void* wb, const float* bias, float* out, const float* mask_ref,
                              void* out_hi, void* out_lo, void* stream) {
     MH_REQUIRE(out_hi && out_lo, MH_ERR_ARG, "mh_conv2d_sh4: both output planes");
-    MH_REQUIRE(mh_aligned16(out_hi) && mh_aligned16(out_lo), MH_ERR_ALIGN, "mh_conv2d_sh4: output planes must be 16-byte aligned");
-    HeadOuts h{nullptr, 0, nullptr, 0, nullptr};
-    h.out_lo = out_lo;
-    return conv_entry(d, in, w, nullptr, wb, bias, out, mask_ref, stream, out_hi, &h);
+    HeadOuts h;
+    h.entry = "mh_conv2d_sh4"; h.out_shadow = out_hi; h.out_lo = out_lo;
+    return conv_entry(d, in, w, wb, bias, out, mask_ref, stream, h);
 }
 extern "C" int mh_conv2d_takes_shadows(const mh_conv_desc* d, const float* in, const float* w, const void* wb, float* out, const float* mask_ref) {
-    HeadOuts h{nullptr, 0, nullptr, 0, nullptr};
-    h.query = 1;
-    return conv_entry(d, in, w, nullptr, wb, nullptr, out, mask_ref, nullptr, nullptr, &h);
+    HeadOuts h;
+    h.entry = "mh_conv2d_takes_shadows"; h.query = 1;
+    return conv_entry(d, in, w, wb, nullptr, out, mask_ref, nullptr, h);
 }
 extern "C" int mh_conv2d_head(const mh_conv_desc* d, const float* in, const float* w, const float* bias, float* out,
                               float* out2, int32_t out2_ld, float* out3, int32_t out3_ld, void* stream) {
     MH_REQUIRE(d && d->N == 1 && d->mode == 0, MH_ERR_ARG, "mh_conv2d_head: a forward conv with ONE output channel");
     MH_REQUIRE((!out2 || out2_ld >= 1) && (!out3 || out3_ld >= 1), MH_ERR_ARG, "mh_conv2d_head: pixel strides of the extra outputs must be >= 1");
-    const HeadOuts h{out2, out2_ld, out3, out3_ld, nullptr};
-    return conv_entry(d, in, w, nullptr, nullptr, bias, out, nullptr, stream, nullptr, &h);
+    HeadOuts h;
+    h.entry = "mh_conv2d_head"; h.out2 = out2; h.out2_ld = out2_ld; h.out3 = out3; h.out3_ld = out3_ld;
+    return conv_entry(d, in, w, nullptr, bias, out, nullptr, stream, h);
 }
-static int conv_entry(const mh_conv_desc* d, const float* in, const float* w, const float* wt, const void* wb, const float* bias,
-                      float* out, const float* mask_ref, void* stream, void* out_shadow, const HeadOuts* head) {
+
+// ---- the route: which kernel family runs a layer, and what that family does with the bf16 shadows ------------------------------------------------------
+// Decided ONCE per call, for the launch, for the mh_conv2d_takes_shadows query (madnet_hip/elision.py drops an fp32 store only on its promise) and for the
+// refusal of the MH_CONV_*_F32_STALE flags (the net under that promise: the dispatch is re-decided on every eager replay from process-wide tuning hooks, so
+// a plan recorded under other settings must fail loudly instead of reading a tensor nobody stored).
+// The families in dispatch order; DESIGN.md section 3 has the table of what each does.
+enum ConvFamily { N1, K1_DGRAD, ROWS, THIN, BANK_SMALL, PATCH, TILED };
+struct ConvRoute {
+    ConvFamily fam;
+    bool stages_in, reads_mask, shadow_only;      // what THIS launch does with in_shadow / mask_shadow / MH_CONV_SHADOW_ONLY (a query: as if both were offered)
+    bool advertises;                              // whether mh_conv2d_takes_shadows reports it
+    bool writes_shadow, writes_lo;                // epilogue stores; else the cast / split launch behind it
+    bool maskless_stale_ok;                       // MH_CONV_MASK_F32_STALE on a launch without mask_ref: nothing to read, accepted (else any stale flag is refused)
+};
+static ConvRoute conv_route(const ConvArgs& a, const HeadOuts& h) {
+    ConvRoute r{};
+    r.fam = conv_n1_ok(a) ? N1 : conv_k1_dgrad_ok(a) ? K1_DGRAD : mh_conv_rows_ok(a) ? ROWS : conv_thin_ok(a) ? THIN :
+            mh_conv_bank_small_ok(a) ? BANK_SMALL : mh_conv_patch_ok(a) ? PATCH : TILED;
+    // a shadow can stand in for its fp32 tensor in a bf16 input gradient, where it is offered and addressable; the mask's only over the whole channel range
+    const bool dgrad16 = a.mode == 1 && a.bf16;
+    const bool in_sh = dgrad16 && (h.query || h.in_shadow) && conv_shadow_bytes(a.B, a.Hi, a.Wi, a.K);
+    const bool mask_sh = dgrad16 && (h.query || h.mask_shadow) && a.mask_ref && conv_shadow_bytes(a.B, a.Ho, a.Wo, a.N) && a.mask_c0 == 0 && a.mask_c1 == a.N;
+    r.advertises = true;
+    switch (r.fam) {
+    case N1: case THIN: break;
+    case K1_DGRAD: case BANK_SMALL: r.writes_shadow = true; break;
+    case ROWS:
+        r.writes_shadow = r.maskless_stale_ok = true;
+        r.stages_in = r.reads_mask = in_sh && mask_sh;       // (the row kernel takes both or neither)
+        r.advertises = false;        // KEPT AS IT IS: the row kernel stages what it is given but the query never said so, so elision keeps the fp32 stores in front of it
+        break;
+    case PATCH:
+        r.writes_shadow = r.maskless_stale_ok = true;
+        r.stages_in = in_sh; r.reads_mask = mask_sh;
+        r.shadow_only = dgrad16 && (h.flags & MH_CONV_SHADOW_ONLY) && h.out_shadow && !a.accumulate;
+        break;
+    case TILED:
+        r.writes_shadow = a.vecC != 0;         // the vector epilogue has the stores (hi and, where asked for, lo)
+        r.writes_lo = a.vecC && h.out_shadow && h.out_lo;
+        r.maskless_stale_ok = true;
+        break;
+    }
+    return r;
+}
+
+static int conv_entry(const mh_conv_desc* d, const float* in, const float* w, const void* wb, const float* bias,
+                      float* out, const float* mask_ref, void* stream, const HeadOuts& h) {
+    MH_REQUIRE(mh_aligned16(h.out_shadow), MH_ERR_ALIGN, "%s: the output shadow (hi plane) must be 16-byte aligned", h.entry);
+    MH_REQUIRE(mh_aligned16(h.out_lo), MH_ERR_ALIGN, "%s: the output lo plane must be 16-byte aligned", h.entry);
+    MH_REQUIRE(mh_aligned16(h.in_shadow), MH_ERR_ALIGN, "%s: in_shadow must be 16-byte aligned", h.entry);
+    MH_REQUIRE(mh_aligned16(h.mask_shadow), MH_ERR_ALIGN, "%s: mask_shadow must be 16-byte aligned", h.entry);
     MH_REQUIRE(d && in && w && out, MH_ERR_ARG, "mh_conv2d: null argument");
+    MH_REQUIRE(!(h.flags & MH_CONV_SHADOW_ONLY) || (h.out_shadow && !d->accumulate), MH_ERR_ARG, "%s: MH_CONV_SHADOW_ONLY needs out_shadow and no accumulation", h.entry);
     MH_REQUIRE(d->B > 0 && d->Hi > 0 && d->Wi > 0 && d->Ho > 0 && d->Wo > 0 && d->K > 0 && d->N > 0,
                MH_ERR_ARG, "mh_conv2d: non-positive dimension");
     MH_REQUIRE(d->kh > 0 && d->kw > 0 && d->kh * d->kw <= 64, MH_ERR_ARG, "mh_conv2d: kernel %dx%d unsupported", d->kh, d->kw);
@@ -1305,78 +1350,36 @@ static int conv_entry(const mh_conv_desc* d, const float* in, const float* w, co
     // launch behind the others
     a.shadow = nullptr; a.shadow_ld = (d->N + 31) / 32 * 32; a.shadow_done = 0;
     a.shadow_lo = nullptr; a.shadow_lo_done = 0;
-    void* const out_lo = head ? head->out_lo : nullptr;
+    const ConvRoute r = conv_route(a, h);
+    if (h.query) return r.advertises && r.stages_in ? 1 | (r.reads_mask ? 2 : 0) : 0;        // (the mask bit is only ever reported with the input bit)
+    if (h.out2 || h.out3) {
+        MH_REQUIRE(r.fam == N1, MH_ERR_UNSUPPORTED, "mh_conv2d_head: the layer does not fit the single-output-channel kernel (Cin %% 4, aligned operands, <= 64 KB of weights)");
+        a.out2 = h.out2; a.out2_ld = h.out2_ld; a.out3 = h.out3; a.out3_ld = h.out3_ld;
+    }
+    // MH_CONV_IN_F32_STALE / MH_CONV_MASK_F32_STALE: the caller elided the fp32 tensor (only its bf16 shadow is valid): a route that would read it is refused
+    MH_REQUIRE(!(h.flags & MH_CONV_IN_F32_STALE) || r.stages_in, MH_ERR_UNSUPPORTED,
+               "mh_conv2d_sh3: the fp32 input was elided (MH_CONV_IN_F32_STALE) but the dispatched kernel does not stage in_shadow");
+    MH_REQUIRE(!(h.flags & MH_CONV_MASK_F32_STALE) || r.reads_mask || (!mask_ref && r.maskless_stale_ok), MH_ERR_UNSUPPORTED,
+               "mh_conv2d_sh3: the fp32 mask was elided (MH_CONV_MASK_F32_STALE) but the dispatched kernel does not read mask_shadow");
+    if (r.stages_in) { a.in_shadow = (const unsigned short*)h.in_shadow; a.in_shadow_bytes = conv_shadow_bytes(a.B, a.Hi, a.Wi, a.K); }
+    if (r.reads_mask) { a.mask_shadow = (const unsigned short*)h.mask_shadow; a.mask_shadow_bytes = conv_shadow_bytes(a.B, a.Ho, a.Wo, a.N); a.mask_shadow_ld = a.shadow_ld; }
+    a.no_f32_out = r.shadow_only;
+    if (r.writes_shadow) a.shadow = (unsigned short*)h.out_shadow;
+    if (r.writes_lo) a.shadow_lo = (unsigned short*)h.out_lo;
     hipStream_t hs = (hipStream_t)stream;
-    int rc;
-    if (head && head->query) {
-        // mh_conv2d_takes_shadows: would this launch stage the bf16 shadow of its input (and honour the shadow-only options)?  Same dispatch order
-        // as below: only the patch-staged input-gradient kernel does.
-        if (conv_n1_ok(a) || conv_k1_dgrad_ok(a) || mh_conv_rows_ok(a) || conv_thin_ok(a) || mh_conv_bank_small_ok(a)) return 0;
-        if (!(mh_conv_patch_ok(a) && a.mode == 1 && a.bf16)) return 0;
-        // (the same byte bounds as the launch below: a shadow of 2 GiB or more is not staged)
-        const int64_t sbq = (int64_t)d->B * d->Hi * d->Wi * ((d->K + 31) / 32 * 32) * 2, mbq = (int64_t)d->B * d->Ho * d->Wo * ((d->N + 31) / 32 * 32) * 2;
-        if (sbq >= (1ll << 31) - 64) return 0;
-        const bool mask_sh = mask_ref && mbq < (1ll << 31) - 64 && d->mask_c0 == 0 && (d->mask_c1 == 0 || d->mask_c1 == d->N);
-        return 1 | (mask_sh ? 2 : 0);
+    int rc = 0;
+    switch (r.fam) {
+    case N1: rc = launch_conv_n1(a, hs); break;
+    case K1_DGRAD: rc = launch_conv_k1_dgrad(a, hs); break;
+    case ROWS: rc = mh_conv_rows_launch(a, hs); break;
+    case THIN: rc = launch_conv_thin(a, hs); break;
+    case BANK_SMALL: rc = mh_conv_bank_small_launch(a, hs); break;
+    case PATCH: rc = mh_conv_patch_launch(a, hs); break;
+    case TILED: rc = conv_dispatch(a, hs); break;
     }
-    // MH_CONV_IN_F32_STALE / MH_CONV_MASK_F32_STALE: the caller elided the fp32 tensor (only its bf16 shadow is valid): a launch whose kernel would read the
-    // fp32 tensor is refused -- the dispatch is re-decided on every eager replay from process-wide tuning hooks, so a plan recorded under other
-    // settings must fail loudly instead of reading a tensor nobody stored
-    auto stale_ok = [&]() -> bool {
-        if (!head) return true;
-        if ((head->flags & MH_CONV_IN_F32_STALE) && !a.in_shadow) { mh_set_error("mh_conv2d_sh3: the fp32 input was elided (MH_CONV_IN_F32_STALE) but the dispatched kernel does not stage in_shadow"); return false; }
-        if ((head->flags & MH_CONV_MASK_F32_STALE) && mask_ref && !a.mask_shadow) { mh_set_error("mh_conv2d_sh3: the fp32 mask was elided (MH_CONV_MASK_F32_STALE) but the dispatched kernel does not read mask_shadow"); return false; }
-        return true;
-    };
-    if (head && (head->out2 || head->out3)) {
-        MH_REQUIRE(conv_n1_ok(a), MH_ERR_UNSUPPORTED, "mh_conv2d_head: the layer does not fit the single-output-channel kernel (Cin %% 4, aligned operands, <= 64 KB of weights)");
-        a.out2 = head->out2; a.out2_ld = head->out2_ld; a.out3 = head->out3; a.out3_ld = head->out3_ld;
-    }
-    const bool stale_any = head && (head->flags & (MH_CONV_IN_F32_STALE | MH_CONV_MASK_F32_STALE));
-    if (stale_any && (conv_n1_ok(a) || conv_k1_dgrad_ok(a) || (!mh_conv_rows_ok(a) && (conv_thin_ok(a) || mh_conv_bank_small_ok(a))))) { stale_ok(); rc = MH_ERR_UNSUPPORTED; }
-    else if (conv_n1_ok(a)) rc = launch_conv_n1(a, hs);
-    else if (conv_k1_dgrad_ok(a)) { a.shadow = (unsigned short*)out_shadow; a.shadow_done = 1; rc = launch_conv_k1_dgrad(a, hs); }
-    else if (mh_conv_rows_ok(a)) {
-        a.shadow = (unsigned short*)out_shadow; a.shadow_done = 1;
-        if (head && head->in_shadow && head->mask_shadow && mask_ref && a.mode == 1 && a.bf16 && d->mask_c0 == 0 && (d->mask_c1 == 0 || d->mask_c1 == d->N)) {
-            // input AND mask from bf16 shadows (the row kernel takes both or neither)
-            const int64_t sb = (int64_t)d->B * d->Hi * d->Wi * ((d->K + 31) / 32 * 32) * 2, mb = (int64_t)d->B * d->Ho * d->Wo * ((d->N + 31) / 32 * 32) * 2;
-            if (sb < (1ll << 31) - 64 && mb < (1ll << 31) - 64) {
-                a.in_shadow = (const unsigned short*)head->in_shadow; a.in_shadow_bytes = (unsigned)sb;
-                a.mask_shadow = (const unsigned short*)head->mask_shadow; a.mask_shadow_bytes = (unsigned)mb; a.mask_shadow_ld = (d->N + 31) / 32 * 32;
-            }
-        }
-        rc = stale_ok() ? mh_conv_rows_launch(a, hs) : MH_ERR_UNSUPPORTED;
-    }
-    else if (conv_thin_ok(a)) rc = launch_conv_thin(a, hs);
-    else if (mh_conv_bank_small_ok(a)) { a.shadow = (unsigned short*)out_shadow; a.shadow_done = 1; rc = mh_conv_bank_small_launch(a, hs); }
-    else if (mh_conv_patch_ok(a)) {
-        a.shadow = (unsigned short*)out_shadow; a.shadow_done = 1;
-        if (head && head->in_shadow && a.mode == 1 && a.bf16) {          // (only this family stages a shadow; the others read the fp32 tensor)
-            const int64_t sb = (int64_t)d->B * d->Hi * d->Wi * ((d->K + 31) / 32 * 32) * 2;
-            if (sb < (1ll << 31) - 64) { a.in_shadow = (const unsigned short*)head->in_shadow; a.in_shadow_bytes = (unsigned)sb; }
-        }
-        if (head && a.mode == 1 && a.bf16) {
-            const int sld = (d->N + 31) / 32 * 32;
-            const int64_t mb = (int64_t)d->B * d->Ho * d->Wo * sld * 2;
-            if (head->mask_shadow && mask_ref && mb < (1ll << 31) - 64 && d->mask_c0 == 0 && (d->mask_c1 == 0 || d->mask_c1 == d->N)) {
-                a.mask_shadow = (const unsigned short*)head->mask_shadow; a.mask_shadow_bytes = (unsigned)mb; a.mask_shadow_ld = sld;
-            }
-            if ((head->flags & 1) && out_shadow && !d->accumulate) a.no_f32_out = 1;
-        }
-        rc = stale_ok() ? mh_conv_patch_launch(a, hs) : MH_ERR_UNSUPPORTED;
-    }
-    else if (!stale_ok()) rc = MH_ERR_UNSUPPORTED;
-    else {
-        if (a.vecC) {      // the tiled kernel's vector epilogue has the stores (hi and, where asked for, lo)
-            a.shadow = (unsigned short*)out_shadow; a.shadow_done = 1;
-            if (out_shadow && out_lo) { a.shadow_lo = (unsigned short*)out_lo; a.shadow_lo_done = 1; }
-        }
-        rc = conv_dispatch(a, hs);
-    }
-    if (!rc && out_shadow && out_lo && !a.shadow_lo_done)       // a family without the lo store: one split launch behind it (hi rewritten with the same bits)
-        rc = mh_plane_split_one(out, d->out_ld, d->N, out_shadow, out_lo, a.shadow_ld, (int64_t)d->B * d->Ho * d->Wo, hs);
-    else if (!rc && out_shadow && !a.shadow_done)
-        rc = mh_shadow_cast_one(out, d->out_ld, d->N, out_shadow, a.shadow_ld, (int64_t)d->B * d->Ho * d->Wo, hs);
+    if (!rc && h.out_shadow && h.out_lo && !r.writes_lo)       // a family without the lo store: one split launch behind it (hi rewritten with the same bits)
+        rc = mh_plane_split_one(out, d->out_ld, d->N, h.out_shadow, h.out_lo, a.shadow_ld, (int64_t)d->B * d->Ho * d->Wo, hs);
+    else if (!rc && h.out_shadow && !r.writes_shadow)
+        rc = mh_shadow_cast_one(out, d->out_ld, d->N, h.out_shadow, a.shadow_ld, (int64_t)d->B * d->Ho * d->Wo, hs);
     return rc;
 }

@@ -1,4 +1,4 @@
-// conv_args.h -- kernel argument block shared by the convolution translation units (conv.hip, conv_patch.hip)
+// conv_args.h -- kernel argument block shared by the convolution translation units (conv.hip, conv_patch.hip, conv_rows.hip)
 #pragma once
 #include "mh_common.h"
 
@@ -7,13 +7,13 @@ struct ConvArgs {
     const void* wb; unsigned wb_bytes;     // fragment bank of w (mh_pack_weights), or null
     unsigned short* shadow; int shadow_ld; // != null: the epilogue also writes bf16(out) to shadow[pixel][shadow_ld] (operand of mh_wgrad_stream)
     unsigned short* shadow_lo;             // != null (with shadow): the epilogue also writes bf16(out - bf16(out)): shadow / shadow_lo = the hi / lo planes mh_conv2d_planes reads
-    int shadow_lo_done;                    // set where a kernel family's epilogue wrote it (else conv_entry splits afterwards)
+    int shadow_lo_done;                    // unused (conv_entry's route knows which families have the store): kept for the layout of the block the kernels were built for
     const unsigned short* in_shadow; unsigned in_shadow_bytes;   // != null: bf16 shadow of `in` (pixel stride = K rounded up to 32, zero padded): the patch-staged
                                                                  // input-gradient kernel stages it as it is instead of converting the fp32 tensor
     const unsigned short* mask_shadow; unsigned mask_shadow_bytes; int mask_shadow_ld;   // != null: the leaky mask reads the bf16 shadow of mask_ref (sign test only)
     int no_f32_out;                      // 1: only the bf16 shadow of the result is stored (the consumers take the shadow; needs shadow, no accumulate)
     float* out2; float* out3; int out2_ld, out3_ld;   // single-output-channel forward conv (mh_conv2d_head): copies of the result (a concat slot, the next stage's accumulator)
-    int shadow_done;                       // set by the launcher of a kernel family whose epilogue wrote the shadow (else conv_entry casts afterwards)
+    int shadow_done;                       // unused, as shadow_lo_done
 #ifdef MH_PHASE_TIMING
     unsigned long long* dbg;                // experiment build only (scripts/exp/phase_timing.sh): per-workgroup phase time stamps
 #endif
@@ -39,6 +39,12 @@ struct ConvArgs {
     int ncls;               // 0 = off
     struct Cls { int py, px, Hq, Wq, M, tile0, ntaps, pad; signed char dy[16], dx[16]; unsigned char id[16]; } cls[4];
 };
+
+// bytes of a bf16 shadow (B x H x W pixels of C channels rounded up to 32), or 0 where the kernels' 32-bit buffer offsets cannot address it (2 GiB - 64 or more)
+static inline unsigned conv_shadow_bytes(int B, int H, int W, int C) {
+    const int64_t bytes = (int64_t)B * H * W * ((C + 31) / 32 * 32) * 2;
+    return bytes < (1ll << 31) - 64 ? (unsigned)bytes : 0u;
+}
 
 // conv_patch.hip: patch-staged bf16 kernel for the stride-1 3x3 (dilated) layers
 bool mh_conv_patch_ok(const ConvArgs& a);

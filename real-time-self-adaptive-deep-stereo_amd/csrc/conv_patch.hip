@@ -1031,13 +1031,7 @@ template <int WM, int WN, int MT, int NT, bool DGRAD, int CPTC = 0, bool X3 = fa
 int launch_patch(ConvArgs& a, hipStream_t s) {
     constexpr int BM = WM * MT * 16, BN = WN * NT * 16, TH = BM / 16;
     static std::atomic<uint64_t> attr_done{0};
-    const uint64_t attr_dev = mh_device_bit();
-    if (!(attr_done.load(std::memory_order_relaxed) & attr_dev)) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_patch_kernel<WM, WN, MT, NT, DGRAD, CPTC, X3>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)PATCH_LDS_MAX);
-        if (e != hipSuccess) { mh_set_error("conv_patch: hipFuncSetAttribute: %s", hipGetErrorString(e)); return (int)e; }
-        attr_done.fetch_or(attr_dev);
-    }
+    if (int rc = mh_lds_optin(attr_done, reinterpret_cast<const void*>(&conv_patch_kernel<WM, WN, MT, NT, DGRAD, CPTC, X3>), (int)PATCH_LDS_MAX, "conv_patch")) return rc;
     if (a.M < 0) return 0;
     PatchGeo g;
     g.TH = TH;
@@ -1073,13 +1067,7 @@ template <int WM, int WN, int MT, int NT, bool X3>
 int launch_bank(ConvArgs& a, hipStream_t s) {
     constexpr int BM = WM * MT * 16, BN = WN * NT * 16, TH = BM / 16;
     static std::atomic<uint64_t> attr_done{0};
-    const uint64_t attr_dev = mh_device_bit();
-    if (!(attr_done.load(std::memory_order_relaxed) & attr_dev)) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_bank_kernel<WM, WN, MT, NT, X3>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)PATCH_LDS_MAX);
-        if (e != hipSuccess) { mh_set_error("conv_bank: hipFuncSetAttribute: %s", hipGetErrorString(e)); return (int)e; }
-        attr_done.fetch_or(attr_dev);
-    }
+    if (int rc = mh_lds_optin(attr_done, reinterpret_cast<const void*>(&conv_bank_kernel<WM, WN, MT, NT, X3>), (int)PATCH_LDS_MAX, "conv_bank")) return rc;
     if (a.M < 0) return 0;
     PatchGeo g;
     g.TH = TH;
@@ -1115,13 +1103,7 @@ std::atomic<int> g_bank_small_place{-1};          // mh_tune_conv_bank_small: wo
 template <bool DGRAD, int PL>
 int launch_bank_small(ConvArgs& a, hipStream_t s) {
     static std::atomic<uint64_t> attr_done{0};
-    const uint64_t attr_dev = mh_device_bit();
-    if (!(attr_done.load(std::memory_order_relaxed) & attr_dev)) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_bank_small_kernel<DGRAD, PL>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)PATCH_LDS_MAX);
-        if (e != hipSuccess) { mh_set_error("conv_bank_small: hipFuncSetAttribute: %s", hipGetErrorString(e)); return (int)e; }
-        attr_done.fetch_or(attr_dev);
-    }
+    if (int rc = mh_lds_optin(attr_done, reinterpret_cast<const void*>(&conv_bank_small_kernel<DGRAD, PL>), (int)PATCH_LDS_MAX, "conv_bank_small")) return rc;
     if (a.M < 0) return 0;
     PatchGeo g;
     g.TH = 2;

@@ -926,29 +926,27 @@ __global__ __launch_bounds__(256) void plane_split_kernel(const mh_plane_seg* __
 std::atomic<int> g_planes_mode{0};       // mh_tune_conv_planes: bits 0-3 tile variant (0 = heuristic), bits 4 / 5 / 6 staggered tiles (dispatch_planes), bits 8 .. 15 timing experiments (PlanesArgs::dbg)
 std::atomic<int> g_planes_launches{0};
 
+// the grid of a launcher's tile counts (a.tiles_y / tiles_x / ntiles_n) over the d x d lattice phases and the images, and the workgroup decode of it
+static int planes_grid(PlanesArgs& a, int d) {
+    a.nwg = a.B * d * d * a.tiles_y * a.tiles_x * a.ntiles_n;
+    const int dmax = std::max(std::max(a.ntiles_n, a.tiles_x), std::max(a.tiles_y, d));
+    MH_REQUIRE(mh_fastdiv_ok((int64_t)a.nwg, dmax), MH_ERR_UNSUPPORTED, "tile decode: %lld workgroups x divisor %d exceeds the 2^32 range of the magic-multiplier division", (long long)a.nwg, dmax);
+    a.dec = mh_make_tile_decode(a.ntiles_n, a.tiles_x, a.tiles_y, d);
+    return 0;
+}
+
 template <int MC, int WM, int WN, int MBW, int K16, int PL>
 int launch_planes(PlanesArgs& a, hipStream_t s, bool attr_only) {
     using G = PlanesGeo<MC, WM, WN, MBW, K16, PL>;
     static_assert(G::LDS <= 160 * 1024, "patch planes exceed the LDS");
     static std::atomic<uint64_t> attr_done{0};
-    const uint64_t attr_dev = mh_device_bit();
-    if (!(attr_done.load(std::memory_order_relaxed) & attr_dev)) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_planes_kernel<MC, WM, WN, MBW, K16, PL>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        if (e != hipSuccess) { mh_set_error("conv_planes: hipFuncSetAttribute: %s", hipGetErrorString(e)); return (int)e; }
-        attr_done.fetch_or(attr_dev);
-    }
+    if (int rc = mh_lds_optin(attr_done, reinterpret_cast<const void*>(&conv_planes_kernel<MC, WM, WN, MBW, K16, PL>), 160 * 1024, "conv_planes")) return rc;
     if (attr_only) return 0;
     const int d = a.dil;
     a.tiles_y = mh_cdiv(mh_cdiv(a.H, d), G::TR);
     a.tiles_x = mh_cdiv(mh_cdiv(a.W, d), MC);
     a.ntiles_n = mh_cdiv(a.N, G::BN);
-    a.nwg = a.B * d * d * a.tiles_y * a.tiles_x * a.ntiles_n;
-    {
-        const int64_t nwg64 = (int64_t)a.nwg;
-        const int dmax = std::max(std::max(a.ntiles_n, a.tiles_x), std::max(a.tiles_y, (int)d));
-        MH_REQUIRE(mh_fastdiv_ok(nwg64, dmax), MH_ERR_UNSUPPORTED, "tile decode: %lld workgroups x divisor %d exceeds the 2^32 range of the magic-multiplier division", (long long)nwg64, dmax);
-    }
-    a.dec = mh_make_tile_decode(a.ntiles_n, a.tiles_x, a.tiles_y, d);
+    if (int rc = planes_grid(a, d)) return rc;
     a.dbg = (g_planes_mode.load(std::memory_order_relaxed) >> 8) & 255;
     ++g_planes_launches;
     mh_note_kernel("conv_planes_kernel<MC=%d,%dx%d waves,MBW=%d,K16=%d,%s> tile %dx%d K=%d dil=%d grid %d lds %d", MC, WM, WN, MBW, K16, PL == 2 ? "bf16x3" : "bf16",
@@ -962,24 +960,13 @@ int launch_planes_stg(PlanesArgs& a, hipStream_t s, bool attr_only) {
     using G = PlanesStgGeo<MC, WN, MBW, K16, PL>;
     static_assert(G::LDS_STG <= 160 * 1024, "patch planes + the waves' transposition blocks exceed the LDS");
     static std::atomic<uint64_t> attr_done{0};
-    const uint64_t attr_dev = mh_device_bit();
-    if (!(attr_done.load(std::memory_order_relaxed) & attr_dev)) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_planes_kernel_stg<MC, WN, MBW, K16, PL>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        if (e != hipSuccess) { mh_set_error("conv_planes (staggered): hipFuncSetAttribute: %s", hipGetErrorString(e)); return (int)e; }
-        attr_done.fetch_or(attr_dev);
-    }
+    if (int rc = mh_lds_optin(attr_done, reinterpret_cast<const void*>(&conv_planes_kernel_stg<MC, WN, MBW, K16, PL>), 160 * 1024, "conv_planes (staggered)")) return rc;
     if (attr_only) return 0;
     const int d = a.dil;
     a.tiles_y = mh_cdiv(mh_cdiv(a.H, d), G::TR);
     a.tiles_x = mh_cdiv(mh_cdiv(a.W, d), MC);
     a.ntiles_n = mh_cdiv(a.N, G::BN);
-    a.nwg = a.B * d * d * a.tiles_y * a.tiles_x * a.ntiles_n;
-    {
-        const int64_t nwg64 = (int64_t)a.nwg;
-        const int dmax = std::max(std::max(a.ntiles_n, a.tiles_x), std::max(a.tiles_y, (int)d));
-        MH_REQUIRE(mh_fastdiv_ok(nwg64, dmax), MH_ERR_UNSUPPORTED, "tile decode: %lld workgroups x divisor %d exceeds the 2^32 range of the magic-multiplier division", (long long)nwg64, dmax);
-    }
-    a.dec = mh_make_tile_decode(a.ntiles_n, a.tiles_x, a.tiles_y, d);
+    if (int rc = planes_grid(a, d)) return rc;
     a.dbg = (g_planes_mode.load(std::memory_order_relaxed) >> 8) & 255;
     ++g_planes_launches;
     mh_note_kernel("conv_planes_kernel<MC=%d,2x%d waves staggered,MBW=%d,K16=%d,%s> tile %dx%d K=%d dil=%d grid %d lds %d", MC, WN, MBW, K16, PL == 2 ? "bf16x3" : "bf16",
@@ -993,24 +980,13 @@ int launch_planes_ck(PlanesArgs& a, hipStream_t s, bool attr_only) {
     using G = PlanesCkGeo<MC, WM, WN, MBW, K16, PL, NBUF>;
     static_assert(G::LDS_CK <= 160 * 1024, "patch buffers exceed the LDS");
     static std::atomic<uint64_t> attr_done{0};
-    const uint64_t attr_dev = mh_device_bit();
-    if (!(attr_done.load(std::memory_order_relaxed) & attr_dev)) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_planes_ck_kernel<MC, WM, WN, MBW, K16, PL, NBUF>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        if (e != hipSuccess) { mh_set_error("conv_planes_ck: hipFuncSetAttribute: %s", hipGetErrorString(e)); return (int)e; }
-        attr_done.fetch_or(attr_dev);
-    }
+    if (int rc = mh_lds_optin(attr_done, reinterpret_cast<const void*>(&conv_planes_ck_kernel<MC, WM, WN, MBW, K16, PL, NBUF>), 160 * 1024, "conv_planes_ck")) return rc;
     if (attr_only) return 0;
     const int d = a.dil;
     a.tiles_y = mh_cdiv(mh_cdiv(a.H, d), G::TR);
     a.tiles_x = mh_cdiv(mh_cdiv(a.W, d), MC);
     a.ntiles_n = mh_cdiv(a.N, G::BN);
-    a.nwg = a.B * d * d * a.tiles_y * a.tiles_x * a.ntiles_n;
-    {
-        const int64_t nwg64 = (int64_t)a.nwg;
-        const int dmax = std::max(std::max(a.ntiles_n, a.tiles_x), std::max(a.tiles_y, (int)d));
-        MH_REQUIRE(mh_fastdiv_ok(nwg64, dmax), MH_ERR_UNSUPPORTED, "tile decode: %lld workgroups x divisor %d exceeds the 2^32 range of the magic-multiplier division", (long long)nwg64, dmax);
-    }
-    a.dec = mh_make_tile_decode(a.ntiles_n, a.tiles_x, a.tiles_y, d);
+    if (int rc = planes_grid(a, d)) return rc;
     a.nchunks = mh_cdiv(mh_cdiv(a.K, 16), K16);
     a.dbg = 0;
     ++g_planes_launches;
@@ -1028,22 +1004,11 @@ int launch_planes_s2bwd(PlanesArgs& a, hipStream_t s) {
     constexpr int LDS_P = ((PR * ROWP * 16 + 1023) / 1024) * 1024;
     constexpr int LDS = LDS_P > G::LDS_CS ? LDS_P : G::LDS_CS;
     static std::atomic<uint64_t> attr_done{0};
-    const uint64_t attr_dev = mh_device_bit();
-    if (!(attr_done.load(std::memory_order_relaxed) & attr_dev)) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_planes_s2bwd_kernel<WM, WN, K16, KH>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        if (e != hipSuccess) { mh_set_error("conv_planes_s2bwd: hipFuncSetAttribute: %s", hipGetErrorString(e)); return (int)e; }
-        attr_done.fetch_or(attr_dev);
-    }
+    if (int rc = mh_lds_optin(attr_done, reinterpret_cast<const void*>(&conv_planes_s2bwd_kernel<WM, WN, K16, KH>), 160 * 1024, "conv_planes_s2bwd")) return rc;
     a.tiles_y = mh_cdiv(a.Hin, WM);
     a.tiles_x = mh_cdiv(a.Win, 32);
     a.ntiles_n = mh_cdiv(a.N, G::BN);
-    a.nwg = a.B * a.tiles_y * a.tiles_x * a.ntiles_n;
-    {
-        const int64_t nwg64 = (int64_t)a.nwg;
-        const int dmax = std::max(std::max(a.ntiles_n, a.tiles_x), std::max(a.tiles_y, (int)1));
-        MH_REQUIRE(mh_fastdiv_ok(nwg64, dmax), MH_ERR_UNSUPPORTED, "tile decode: %lld workgroups x divisor %d exceeds the 2^32 range of the magic-multiplier division", (long long)nwg64, dmax);
-    }
-    a.dec = mh_make_tile_decode(a.ntiles_n, a.tiles_x, a.tiles_y, 1);
+    if (int rc = planes_grid(a, 1)) return rc;
     a.dbg = 0;
     ++g_planes_launches;
     mh_note_kernel("conv_planes_s2bwd_kernel<%dx%d waves,K16=%d,%dx%d,bf16> dz tile %dx32 -> dx %dx64, K=%d N=%d grid %d lds %d", WM, WN, K16, KH, KH, WM, 2 * WM, a.K, a.N, a.nwg, LDS);
@@ -1056,23 +1021,12 @@ int launch_planes_s2fwd(PlanesArgs& a, hipStream_t s, bool attr_only) {
     using G = PlanesS2Geo<KH, WN, MBW, K16, PL>;
     static_assert(G::LDS2 <= 160 * 1024, "patch planes exceed the LDS");
     static std::atomic<uint64_t> attr_done{0};
-    const uint64_t attr_dev = mh_device_bit();
-    if (!(attr_done.load(std::memory_order_relaxed) & attr_dev)) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_planes_s2fwd_kernel<KH, WN, MBW, K16, PL>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        if (e != hipSuccess) { mh_set_error("conv_planes_s2fwd: hipFuncSetAttribute: %s", hipGetErrorString(e)); return (int)e; }
-        attr_done.fetch_or(attr_dev);
-    }
+    if (int rc = mh_lds_optin(attr_done, reinterpret_cast<const void*>(&conv_planes_s2fwd_kernel<KH, WN, MBW, K16, PL>), 160 * 1024, "conv_planes_s2fwd")) return rc;
     if (attr_only) return 0;
     a.tiles_y = mh_cdiv(a.H, MBW);
     a.tiles_x = mh_cdiv(a.W, 32);
     a.ntiles_n = mh_cdiv(a.N, WN * 32);
-    a.nwg = a.B * a.tiles_y * a.tiles_x * a.ntiles_n;
-    {
-        const int64_t nwg64 = (int64_t)a.nwg;
-        const int dmax = std::max(std::max(a.ntiles_n, a.tiles_x), std::max(a.tiles_y, 1));
-        MH_REQUIRE(mh_fastdiv_ok(nwg64, dmax), MH_ERR_UNSUPPORTED, "tile decode: %lld workgroups x divisor %d exceeds the 2^32 range of the magic-multiplier division", (long long)nwg64, dmax);
-    }
-    a.dec = mh_make_tile_decode(a.ntiles_n, a.tiles_x, a.tiles_y, 1);
+    if (int rc = planes_grid(a, 1)) return rc;
     a.dbg = 0;
     ++g_planes_launches;
     mh_note_kernel("conv_planes_s2fwd_kernel<%dx%d,1x%d waves,MBW=%d,K16=%d,%s> tile %dx%d K=%d grid %d lds %d", KH, KH, WN, MBW, K16, PL == 2 ? "bf16x3" : "bf16", MBW * 32, WN * 32,

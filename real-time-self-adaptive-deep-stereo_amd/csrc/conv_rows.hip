@@ -279,7 +279,7 @@ bool mh_conv_rows_ok(const ConvArgs& a) {
     if (!(s1 || s2)) return false;
     if (a.ncls != 0 || a.K < 2 || a.K > 16 || a.N > 32 || a.N % 8 != 0 || !a.vecA || !a.vecC) return false;
     if (a.x3 && (a.accumulate || a.mask_ref)) return false;        // (the split-bf16 instances have no registers left for the pre-loaded epilogue operands)
-    if ((int64_t)a.B * a.Ho * a.Wo * ((a.N + 31) / 32 * 32) * 2 >= (1ll << 31) - 64) return false;       // 32-bit offsets into the shadow
+    if (!conv_shadow_bytes(a.B, a.Ho, a.Wo, a.N)) return false;       // 32-bit offsets into the shadow
     return (int64_t)a.B * a.Ho * a.Wo >= minpix;
 }
 

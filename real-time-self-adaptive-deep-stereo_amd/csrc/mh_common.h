@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdio.h>
+#include <atomic>
 #include "../../include/madnet_hip.h"
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
@@ -24,6 +25,18 @@ static inline int mh_cdiv(int64_t a, int64_t b) { return (int)((a + b - 1) / b);
 // hipFuncSetAttribute (the > 64 KiB dynamic-LDS opt-in) applies to the CURRENT device only: the per-instantiation "done" flags are one bit per device
 // id (a function-static bool made the first launch on a second device of the same process fail)
 static inline uint64_t mh_device_bit() { int d = 0; if (hipGetDevice(&d) != hipSuccess) d = 0; return 1ull << (d & 63); }
+// the opt-in itself, once per kernel and device: `done` is the call site's own function-static flag word, `kernel` the instantiation's address.  A kernel
+// that stays within the 64 KiB every launch may use needs no call.  0, or the hipError_t with mh_last_error() set
+static inline int mh_lds_optin(std::atomic<uint64_t>& done, const void* kernel, int bytes, const char* what) {
+    const uint64_t dev = mh_device_bit();
+    if (done.load(std::memory_order_relaxed) & dev) return 0;
+    if (bytes > 64 * 1024) {
+        const hipError_t e = hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
+        if (e != hipSuccess) { mh_set_error("%s: hipFuncSetAttribute: %s", what, hipGetErrorString(e)); return (int)e; }
+    }
+    done.fetch_or(dev);
+    return 0;
+}
 static inline bool mh_aligned16(const void* p) { return (((uintptr_t)p) & 15u) == 0; }
 
 // ---- buffer (SRD) loads with hardware bounds checking --------------------------------------

@@ -1,0 +1,153 @@
+"""Dispatch table of the mh_conv2d* entry points: which kernel family a launch runs, what mh_conv2d_takes_shadows answers for it and which
+MH_CONV_*_F32_STALE launches are refused.  Two commits dispatch alike when their outputs are equal line for line (same library kind: the result hashes
+are the backend's own bits).
+  (a) every kernel family at a small shape, forced with the tuning hooks, LAUNCHED: mode 0 / 1, precision 0 / 1 / 2, with bias, mask, sub-range mask,
+      accumulation, an unaligned output, the lo plane (mh_conv2d_sh4).  One line per case: return code, mh_last_kernel(), query bits, for flags 2 / 4 / 6
+      the return code with / without the shadows and whether the NaN-filled output was written, hash of the result and of its shadow
+  (b) the query alone at every OP_CONV descriptor of the recorded MADNet / DispNet FULL plans at 375x1242 and 320x1216, B = 1 and 4
+Only entry points of ABI 16.  usage: conv_dispatch_table.py [--lib PATH]   (default: the CPU emulator, tests/emul/libmadnet_emul.so; a product library
+runs on cuda:0)"""
+import ctypes as C
+import hashlib
+import os
+import sys
+
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+PKG = os.path.join(ROOT, "real-time-self-adaptive-deep-stereo_amd")
+sys.path[:0] = [ROOT, PKG]
+from madnet_hip import _ffi, ops, engine as E, dispnet_engine as DE      # noqa: E402
+
+# (tag, B, H, W, Cin, Cout of the forward layer, hook name, hook value, value that restores the default, fragment bank)
+FAMILIES = [
+    ("head", 1, 8, 16, 32, 1, None, 0, 0, False),              # (a single-output-channel layer: n1 forward, k1_dgrad in mode 1)
+    ("rows", 1, 8, 32, 16, 16, "tune_conv_rows", 1, -1, False),
+    ("thin", 1, 8, 32, 4, 16, "tune_conv_thin", 1, 0, False),
+    ("thin16", 1, 8, 32, 16, 16, "tune_conv_thin", 1, 0, False),
+    ("bank_small", 1, 8, 16, 32, 32, None, 0, 0, True),
+    ("patch", 1, 12, 20, 64, 64, "tune_conv_patch", 128, -1, False),
+    ("patch38", 1, 12, 20, 38, 64, "tune_conv_patch", 128, -1, False),     # (a padded-row input gradient: ConvArgs::vecCpad)
+    ("tiled", 1, 12, 20, 64, 64, None, 0, 0, False),
+    ("tiled_s2", 1, 12, 20, 32, 32, None, 0, 0, False),
+]
+VARIANTS = ("plain", "bias", "mask", "mask+acc", "submask", "unaligned", "lo")
+
+
+def P(t, off=0):
+    return None if t is None else C.c_void_p(t.data_ptr() + off)
+
+
+def rnd(shape, seed, dev):
+    return torch.randn(*shape, generator=torch.Generator().manual_seed(seed)).bfloat16().float().to(dev)
+
+
+def shadow_of(t):
+    s = torch.zeros(t.shape[:3] + ((t.shape[3] + 31) // 32 * 32,), dtype=torch.bfloat16, device=t.device)
+    s[..., :t.shape[3]] = t.bfloat16()
+    return s
+
+
+def digest(t):
+    return hashlib.sha256(t.detach().cpu().contiguous().view(torch.uint8).numpy().tobytes()).hexdigest()[:12]
+
+
+def launched(lib, dev, sync):
+    raw = lambda name: getattr(lib, "_raw_mh_" + name)
+    for tag, B, H, W, Ci, Co, hook, hook_on, hook_off, banked in FAMILIES:
+        stride = 2 if tag.endswith("_s2") else 1
+        Hs, Ws, pt, pl = ops.conv_geometry(H, W, 3, 3, stride, 1)
+        w = rnd((3, 3, Ci, Co), 1, dev)
+        for mode in (0, 1):
+            # the descriptor's input / output: forward x -> y, input gradient dy -> dx
+            Hi, Wi, Ho, Wo, K, N = (H, W, Hs, Ws, Ci, Co) if mode == 0 else (Hs, Ws, H, W, Co, Ci)
+            ld = lambda c: (c + 3) // 4 * 4 if c > 1 else 1
+            for prec in (0, 1, 2):
+                bank = None
+                keep = []
+                if banked and (prec == 2 and mode == 0 or prec == 1):
+                    planes = 2 if prec == 2 else 1
+                    bank = torch.zeros(ops.pack_bytes(w, planes, mode) // 4, device=dev)
+                    ops.pack_weights(lib, [(w, bank, planes, mode)], dev, keep)
+                for var in VARIANTS:
+                    if var == "bias" and mode == 1:
+                        continue
+                    x = torch.zeros(B, Hi, Wi, ld(K), device=dev); x[..., :K] = rnd((B, Hi, Wi, K), 2, dev)
+                    masked = var in ("mask", "mask+acc", "submask")
+                    mask = None
+                    if masked:
+                        mask = torch.zeros(B, Ho, Wo, ld(N), device=dev); mask[..., :N] = rnd((B, Ho, Wo, N), 3, dev)
+                    bias = rnd((N,), 4, dev) if var == "bias" else None
+                    c0, c1 = (N // 4, N // 2) if var == "submask" and N >= 4 else (0, 0)
+                    d = ops.conv_desc(B, Hi, Wi, Ho, Wo, K, N, 3, 3, stride, 1, pt, pl, mode, mode, ld(K), ld(N), mask_ld=(ld(N) if masked else 0),
+                                      accumulate=int(var == "mask+acc"), alpha=(0.2 if mode == 0 else 1.0), mask_alpha=0.2, mask_c0=c0, mask_c1=c1, precision=prec)
+                    xs, ms = shadow_of(x[..., :K]), (shadow_of(mask[..., :N]) if masked else None)
+                    off = 4 if var == "unaligned" else 0
+
+                    def fresh(fill):
+                        o = torch.full((B * Ho * Wo * ld(N) + 4,), fill, device=dev)
+                        return o, torch.zeros(B, Ho, Wo, (N + 31) // 32 * 32, dtype=torch.bfloat16, device=dev)
+
+                    if hook:
+                        getattr(lib, hook)(hook_on)
+                    try:
+                        bits = raw("conv2d_takes_shadows")(C.byref(d), P(x), P(w), P(bank), P(fresh(0.0)[0], off), P(mask))
+                        out, osh = fresh(1.0)
+                        if var == "lo":
+                            olo = torch.zeros_like(osh)
+                            rc = raw("conv2d_sh4")(C.byref(d), P(x), P(w), P(bank), P(bias), P(out, off), P(mask), P(osh), P(olo), None)
+                        else:
+                            olo = None
+                            rc = raw("conv2d_sh")(C.byref(d), P(x), P(w), P(bank), P(bias), P(out, off), P(mask), P(osh), None)
+                        kernel = lib.last_kernel().decode() if rc == 0 else "-"
+                        sync()
+                        stale = []
+                        for flags in (2, 4, 6):
+                            for shadows in (True, False):
+                                o2, s2 = fresh(float("nan"))
+                                r2 = raw("conv2d_sh3")(C.byref(d), P(x), P(xs) if shadows else None, P(w), P(bank), P(bias), P(o2, off), P(mask),
+                                                       P(ms) if shadows else None, P(s2), flags, None)
+                                k2 = lib.last_kernel().decode().split("<")[0].split(" ")[0] if r2 == 0 else "-"
+                                sync()
+                                stale.append("%d:%s:%d:%s:%s" % (flags, "sh" if shadows else "no", r2, k2, "written" if not torch.isnan(o2).all() else "untouched"))
+                    finally:
+                        if hook:
+                            getattr(lib, hook)(hook_off)
+                    print("a", tag, "mode=%d prec=%d %s" % (mode, prec, var), "rc=%d" % rc, "[%s]" % kernel, "takes=%d" % bits, " ".join(stale),
+                          "out=%s sh=%s lo=%s" % (digest(out), digest(osh), digest(olo) if olo is not None else "-"))
+                    sys.stdout.flush()
+
+
+def queried(lib, dev):
+    q = lib._raw_mh_conv2d_takes_shadows
+    for H, W in ((375, 1242), (320, 1216)):
+        for B in (1, 4):
+            for net, cls in (("madnet", E.MadNetEngine), ("dispnet", DE.DispNetEngine)):
+                for prec in ("fp32", "mixed", "bf16"):
+                    eng = cls(lib, H, W, B=B, device=dev, precision=prec)
+                    plan = eng.build_plan("FULL", lr=1e-4)
+                    for k in range(plan.n):
+                        c = plan.arr[k]
+                        if c.kind != _ffi.OP_CONV:
+                            continue
+                        ints = [c.i[j] for j in range(18)] + [c.i[18], c.f[0], c.f[1], c.i[19], c.i[20], c.i[22]]         # (as elision._takes_shadows)
+                        d = _ffi.ConvDesc(*ints)
+                        bits = q(C.byref(d), C.c_void_p(c.p[0]), C.c_void_p(c.p[1]), C.c_void_p(c.p[6]), C.c_void_p(c.p[3]), C.c_void_p(c.p[4]))
+                        print("b", "%dx%d B=%d %s %s op %d" % (H, W, B, net, prec, k), " ".join(str(v) for v in ints), "bank=%d mask=%d" % (bool(c.p[6]), bool(c.p[4])),
+                              "takes=%d" % bits)
+                    eng.close()
+                    sys.stdout.flush()
+
+
+def main():
+    path = sys.argv[sys.argv.index("--lib") + 1] if "--lib" in sys.argv else os.path.join(ROOT, "tests", "emul", "libmadnet_emul.so")
+    emul = "emul" in os.path.basename(path)
+    dev = "cpu" if emul else "cuda:0"
+    lib = _ffi.Lib(path)
+    lib.ensure_init()
+    launched(lib, dev, (lambda: None) if emul else torch.cuda.synchronize)
+    queried(lib, dev)
+
+
+if __name__ == "__main__":
+    main()

@@ -146,3 +146,83 @@ def test_round3_entry_points_argument_checks(backend):
     refs = (_ffi.PlanRef * 1)(); refs[0].ops, refs[0].nops = C.addressof(op), 1
     assert _raw(backend, "plans_run")(refs, 1, None) < 0 and "lane" in _msg(backend)
     assert _raw(backend, "plans_run")(refs, 0, None) == ERR_ARG
+
+
+def _bf16_exact(shape, seed, dev):
+    g = torch.Generator().manual_seed(seed)
+    return torch.randn(*shape, generator=g).bfloat16().float().to(dev)
+
+
+def _shadow_of(t):
+    """bf16 shadow of an NHWC tensor: pixel stride = channels rounded up to 32, zero padded"""
+    s = torch.zeros(t.shape[:3] + ((t.shape[3] + 31) // 32 * 32,), dtype=torch.bfloat16, device=t.device)
+    s[..., :t.shape[3]] = t.bfloat16()
+    return s
+
+
+# (family, kernel name, B, H, W, reduction channels, output channels, mode, precision, mask, hook)
+_ROUTE_CASES = [
+    ("patch", "conv_patch_kernel", 1, 12, 20, 64, 64, 1, 1, True, ("tune_conv_patch", 128, -1)),
+    ("rows", "conv_rows_kernel", 1, 8, 32, 16, 16, 1, 1, True, ("tune_conv_rows", 1, -1)),
+    ("bank_small", "conv_bank_small_kernel", 1, 8, 16, 32, 32, 1, 1, True, None),
+    ("thin", "conv_thin_kernel", 1, 8, 32, 4, 16, 0, 1, True, ("tune_conv_thin", 1, 0)),
+    ("n1", "conv_n1_fwd_kernel", 1, 8, 16, 32, 1, 0, 0, False, None),            # (the single-output-channel kernel takes no mask)
+    ("k1_dgrad", "conv_k1_dgrad_kernel", 1, 8, 16, 1, 32, 1, 0, True, None),
+    ("tiled", "conv_igemm_kernel", 1, 12, 20, 64, 64, 1, 0, True, None),
+]
+
+
+@pytest.mark.parametrize("case", _ROUTE_CASES, ids=[c[0] for c in _ROUTE_CASES])
+def test_conv_route_query_launch_and_stale_refusal_agree(backend, case):
+    """The contract plan elision relies on, per kernel family of mh_conv2d*: where mh_conv2d_takes_shadows sets the bit of an operand, a launch
+    flagged MH_CONV_*_F32_STALE takes that operand from its bf16 shadow alone (the fp32 tensor is NaN here) and gives the bits of the plain launch;
+    where the bit is clear the flagged launch is refused and writes nothing.  The row kernel is pinned as it is: it answers 0 and stages both
+    shadows when given both.  Operands hold bf16-exact values, so a shadow and its fp32 tensor are the same numbers."""
+    fam, kname, B, H, W, K, N, mode, prec, masked, hook = case
+    dev, lib = backend.device, backend.lib
+    P = lambda t: None if t is None else C.c_void_p(t.data_ptr())
+    IN_STALE, MASK_STALE = 2, 4
+    x = _bf16_exact((B, H, W, K), 11, dev)
+    w = _bf16_exact((3, 3, N, K) if mode else (3, 3, K, N), 12, dev)          # HWIO of the forward conv
+    mask = _bf16_exact((B, H, W, N), 13, dev) if masked else None
+    d = ops.conv_desc(B, H, W, H, W, K, N, 3, 3, 1, 1, 1, 1, mode, mode, K, N, mask_ld=(N if masked else 0), mask_alpha=0.2, precision=prec)
+    xs, ms = _shadow_of(x), (_shadow_of(mask) if masked else None)
+    x_nan = torch.full_like(x, float("nan")); mask_nan = torch.full_like(mask, float("nan")) if masked else None
+    keep, bank = [], None
+    if fam == "bank_small":
+        bank = torch.zeros(ops.pack_bytes(w, 1, 1) // 4, device=dev)
+        ops.pack_weights(lib, [(w, bank, 1, 1)], dev, keep)
+    sh3, q = _raw(backend, "conv2d_sh3"), _raw(backend, "conv2d_takes_shadows")
+
+    def launch(flags, shadows=True, stale=0):
+        out = torch.full((B, H, W, N), float("nan"), device=dev)
+        rc = sh3(C.byref(d), P(x_nan if stale & IN_STALE else x), P(xs) if shadows else None, P(w), P(bank), None, P(out),
+                 P(mask_nan if stale & MASK_STALE else mask), P(ms) if shadows else None, None, flags, None)
+        backend.sync()
+        return rc, out
+
+    if hook:
+        getattr(lib, hook[0])(hook[1])
+    try:
+        bits = q(C.byref(d), P(x), P(w), P(bank), P(torch.empty(B, H, W, N, device=dev)), P(mask))
+        rc, plain = launch(0, shadows=False)
+        assert rc == 0 and kname in lib.last_kernel().decode(), (rc, lib.last_kernel())
+        assert not torch.isnan(plain).any()
+        if fam == "rows":
+            assert bits == 0
+            rc, out = launch(IN_STALE | MASK_STALE, stale=IN_STALE | MASK_STALE)
+            assert rc == 0 and kname in lib.last_kernel().decode() and torch.equal(out, plain)
+            rc, out = launch(IN_STALE | MASK_STALE, shadows=False)
+            assert rc == ERR_UNSUPPORTED and torch.isnan(out).all()
+            return
+        assert bits == (3 if fam == "patch" else 0)
+        for flag, name in ((IN_STALE, "MH_CONV_IN_F32_STALE"),) + (((MASK_STALE, "MH_CONV_MASK_F32_STALE"),) if masked else ()):
+            if bits & (flag >> 1):
+                rc, out = launch(flag, stale=flag)
+                assert rc == 0 and kname in lib.last_kernel().decode() and torch.equal(out, plain), (fam, name, rc)
+            else:
+                rc, out = launch(flag)
+                assert rc == ERR_UNSUPPORTED and name in _msg(backend) and torch.isnan(out).all(), (fam, name, rc, _msg(backend))
+    finally:
+        if hook:
+            getattr(lib, hook[0])(hook[2])
