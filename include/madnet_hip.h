@@ -464,6 +464,11 @@ int mh_reprojection_loss_phase(const float* left, const float* right, const floa
 int64_t mh_metrics_ws_floats(int32_t B, int32_t H, int32_t W);
 int mh_metrics(const float* disp, const float* gt, float* ws, float* result, float pixel_th,
                int32_t B, int32_t H, int32_t W, void* stream);
+/* the report of the continual loop (Stereo_Continual_Adaptation.py:245-249): val = gt > 0, diff = |gt - disp| on val;
+ * result[0] = mean(diff) (EPE), result[1] = 100 * mean(diff > 3 && diff / gt >= 0.05) (KITTI D1-all), result[2] = #val
+ * (no valid pixel: result[0] = result[1] = NaN).  ws: >= mh_metrics_kitti_ws_floats() floats. */
+int64_t mh_metrics_kitti_ws_floats(int32_t B, int32_t H, int32_t W);
+int mh_metrics_kitti(const float* disp, const float* gt, float* ws, float* result, int32_t B, int32_t H, int32_t W, void* stream);
 
 /* ---- proxy-label loss of the continual-adaptation variant: loss_factory.get_proxy_loss('mean_l1', weights=[w]*10)
  *      (Losses/loss_factory.py:304-351, mean_l1 :28-38; Stereo_Continual_Adaptation.py:75,112)
@@ -472,6 +477,14 @@ int mh_metrics(const float* disp, const float* gt, float* ws, float* result, flo
 int64_t mh_proxy_ws_floats(int32_t B, int32_t H, int32_t W);
 int mh_proxy_loss(const float* pred, const float* proxy, float* ws, float* result, float* dpred, float weight,
                   float grad_scale, int32_t B, int32_t H, int32_t W, void* stream);
+/* the same loss at 1/scale resolution -- a MAD block's loss under --reprojectionScale (Stereo_Continual_Adaptation.py:26-27,95-112): with R = the TF1
+ * legacy bilinear resize to (H / scale) x (W / scale) (the arithmetic of mh_resize_fwd mode 0),  p = R(pred),  q = R(proxy) / scale,
+ * valid = !(q <= 0 || q >= 192);  result[0] = weight * sum(valid*|p-q|) / sum(valid);  result[1] = sum(valid);
+ * dpred [B,H,W] (may be NULL) = grad_scale * weight * R^T(valid * sign(p - q)) / sum(valid), every element written.  Neither resized map is stored;
+ * no float atomics (two runs are bit-identical).  ws: mh_proxy_scaled_ws_floats() floats. */
+int64_t mh_proxy_scaled_ws_floats(int32_t B, int32_t H, int32_t W, int32_t scale);
+int mh_proxy_loss_scaled(const float* pred, const float* proxy, float* ws, float* result, float* dpred, float weight,
+                         float grad_scale, int32_t scale, int32_t B, int32_t H, int32_t W, void* stream);
 
 /* ---- offline training (Train.py): supervised mean_l1 per predicted scale and the Adam update -------------------------------
  * mh_supervised_loss: loss_factory.get_supervised_loss('mean_l1', multiScale=True, max_disp=MAX_DISP) term of ONE scale
@@ -557,7 +570,9 @@ enum { MH_OP_CONV = 1, MH_OP_WGRAD, MH_OP_CORR_FWD, MH_OP_CORR_BWD, MH_OP_WARP_F
        MH_OP_WGRAD_PARTIAL, MH_OP_WGRAD_REDUCE, MH_OP_PROXY_LOSS, MH_OP_SUPERVISED_LOSS, MH_OP_ADAM, MH_OP_ADAM_ADVANCE,
        MH_OP_RESIZE_IMAGE, MH_OP_LEVEL_FRONT, MH_OP_RESERVED_25 /* (was: transposed filter banks of the retired LDS-free kernel) */, MH_OP_PACK_W, MH_OP_CORR_WARP_BWD, MH_OP_SHADOW_CAST, MH_OP_WGRAD_STREAM, MH_OP_HEAD_BWD, MH_OP_HEAD_FWD, MH_OP_CONV_PLANES, MH_OP_PLANE_SPLIT, MH_OP_STAMP, MH_OP_CONV_PLANES_BWD, MH_OP_DET_FLUSH, MH_OP_CONV_IMAGE,
        MH_OP_ALLREDUCE /* mh_allreduce_sum: p[0] = comm, p[1 .. i[0]] = buffers, i[1 .. i[0]] = counts (floats, < 2^31 each) */,
-       MH_OP_FETCH_INPUTS /* mh_fetch_inputs: p[0] = table, p[1 .. i[0]] = destinations, i[1 .. i[0]] = counts (floats, < 2^31 each) */ };
+       MH_OP_FETCH_INPUTS /* mh_fetch_inputs: p[0] = table, p[1 .. i[0]] = destinations, i[1 .. i[0]] = counts (floats, < 2^31 each) */,
+       MH_OP_PROXY_LOSS_SCALED /* mh_proxy_loss_scaled: i = B H W scale ; f = weight grad_scale ; p = pred proxy ws result dpred */,
+       MH_OP_METRICS_KITTI /* mh_metrics_kitti: i = B H W ; p = disp gt ws result */ };
 /* i[26] of every op is its scheduling word: low byte = lane (0 = the caller's stream; 1..MH_MAX_LANES-1 = side
  * streams owned by the library: the op is forked from lane 0 right before it, i.e. ordered after everything recorded so
  * far, and runs concurrently with the lane-0 ops that follow); MH_OP_JOIN = lane 0 first waits for all side lanes.

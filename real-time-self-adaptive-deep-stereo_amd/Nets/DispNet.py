@@ -51,7 +51,8 @@ class DispNet(Stereo_net.StereoNet):
         weights = args.get('weights')
         if weights is None:
             weights = synthetic.xavier_weights(dict(DE.dispnet_manifest()), seed=0)
-        self.engine = eng = DE.DispNetEngine(lib, H, W, B=B, device=dev, weights=weights)
+        self.engine = eng = DE.DispNetEngine(lib, H, W, B=B, device=dev, weights=weights,
+                                             precision=args.get('precision', 'fp32'))   # extra kwarg, as Nets/MadNet.py
         self._lib = lib
         P = eng.params
         self._variables = {}

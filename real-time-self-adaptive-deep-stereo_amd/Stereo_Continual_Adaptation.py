@@ -23,7 +23,8 @@ PIXEL_TH = 3
 
 
 def d1_and_epe(disp, gt):
-    """KITTI D1-all and EPE of one frame (Stereo_Continual_Adaptation.py:241-246), on the device tensors."""
+    """KITTI D1-all and EPE of one frame (Stereo_Continual_Adaptation.py:241-246), on the device tensors.  The loop reads the same two numbers from the step
+    itself (Adapter(kitti_metrics=True)); this stays for callers that hold a disparity and a ground truth of their own."""
     val = gt > 0
     diff = (gt[val] - disp[val]).abs()
     if diff.numel() == 0:
@@ -43,22 +44,24 @@ def main(args):
     dev = 'cuda'
     net_args = {'left_img': torch.zeros(1, H, W, 3, device=dev), 'right_img': torch.zeros(1, H, W, 3, device=dev),
                 'split_layers': [None], 'sequence': True, 'train_portion': 'BEGIN',
-                'bulkhead': True if args.mode == 'MAD' else False, 'weights': load_weights(args.weights, args.modelName)}
+                'bulkhead': True if args.mode == 'MAD' else False, 'weights': load_weights(args.weights, args.modelName),
+                'precision': getattr(args, 'precision', 'fp32')}
     stereo_net = Nets.get_stereo_net(args.modelName, net_args)
     print('Stereo Prediction Model:\n', stereo_net)
     adapter = Adapter(stereo_net, mode=args.mode, block_config=train_config, lr=args.lr, sample_mode=args.sampleMode,
                       num_blocks=args.numBlocks, fixed_id=args.fixedID, sample_frequency=args.sampleFrequency,
                       ssim_th=args.SSIMTh, reprojection_scale=args.reprojectionScale, loss='proxy',
-                      dilation=args.dilation, decay=args.decay, uf=args.uf)
+                      dilation=args.dilation, decay=args.decay, uf=args.uf, kitti_metrics=True)
     avg_accumulator, d1_accumulator = [], []
     step = 0
+    t_begin = time.time()
     with open(os.path.join(args.output, 'histogram.csv'), 'w') as f_out:
         f_out.write('Histogram\n')
     try:
         frames = data_reader.device_prefetcher(data_set, dev, depth=3, consumer_stream=adapter.stream, cast=False)
         for left, right, gt, proxy, real_width in frames:
             out = adapter.step(left, right, gt[..., 0], proxy=proxy[..., 0])
-            d1, epe = d1_and_epe(out['disparity'][0], gt[0, ..., 0])
+            d1, epe = out['d1'], out['epe_gt0']          # computed inside the step (mh_metrics_kitti): the loop launches nothing and waits for nothing of its own
             d1_accumulator.append(d1)
             avg_accumulator.append(epe)
             if step % 100 == 0:
@@ -71,8 +74,14 @@ def main(args):
                 dispy_to_save = np.clip(dispy.astype(np.uint16), 0, MAX_DISP)        # (integer disparities * 256, :279-280)
                 Image.fromarray((dispy_to_save * 256).astype(np.uint16)).save(
                     os.path.join(args.output, 'disparities/disparity_{}.png'.format(step)))
+            if getattr(args, 'dumpOutputs', False):
+                np.save(os.path.join(args.output, 'disparities', 'disparity_{}.npy'.format(step)), out['disparity'][0].detach().cpu().numpy())
             step += 1
     finally:
+        wall = time.time() - t_begin
+        # the wall-clock rate of the loop (first frame = plan recording + graph capture included), as Stereo_Online_Adaptation.py reports it
+        with open(os.path.join(args.output, 'wall_clock.csv'), 'w+') as f_out:
+            f_out.write('steps,wall_seconds,wall_FPS\n{},{},{}\n'.format(max(step, 1), wall, max(step, 1) / max(wall, 1e-9)))
         with open(os.path.join(args.output, 'overall.csv'), 'w+') as f_out:
             print(adapter.fetch_counter)
             f_out.write('EPE\tD1\n')
@@ -104,7 +113,7 @@ def build_parser():
     parser.add_argument("--blockConfig", help="json file listing the layers of every trainable portion", required=True)
     parser.add_argument("--sampleMode", help="strategy that picks the portions to train", choices=sampler_factory.AVAILABLE_SAMPLER, default='SAMPLE')
     parser.add_argument("--fixedID", help="portion indices for --sampleMode FIXED", type=int, nargs='+', default=[0])
-    parser.add_argument("--reprojectionScale", help="losses at 1/scale resolution (only 1 is supported here)", default=1, type=int)
+    parser.add_argument("--reprojectionScale", help="MAD mode: the proxy loss of a trained portion is computed on its prediction and the proxy labels resized to 1/scale of the image size (bilinear, without half-pixel centres), the labels divided by scale; the full-resolution loss and the report are unaffected; FULL / NONE ignore it", default=1, type=int)
     parser.add_argument("--summary", help="accepted for compatibility; no TensorBoard summaries are written", action='store_true')
     parser.add_argument("--imageShape", help="height width every frame is centre-cropped / zero-padded to", nargs='+', type=int, default=[320, 1216])
     parser.add_argument("--SSIMTh", help="restore the initial weights when the loss exceeds this value", type=float, default=0.5)
@@ -116,6 +125,8 @@ def build_parser():
     parser.add_argument("--dilation", help="update the weights only every K-th frame", type=int, default=1)
     parser.add_argument("--decay", help="multiplicative decay of the sampling logits", type=float, default=0.99)
     parser.add_argument("--uf", help="gain of the reward added to the logits of the last trained portions", type=float, default=0.01)
+    parser.add_argument("--precision", help="MFMA arithmetic of the conv kernels: fp32 (default; the reference adapts in fp32), mixed (forward within fp32 tolerance, bf16 gradients) or bf16 (opt-in throughput mode)", choices=['fp32', 'mixed', 'bf16'], default='fp32')
+    parser.add_argument("--dumpOutputs", help="also write the float32 disparity of every frame to <output>/disparities/disparity_<step>.npy", action='store_true')
     return parser
 
 
@@ -124,7 +135,7 @@ if __name__ == '__main__':
     if not os.path.exists(args.output):
         os.makedirs(args.output)
     os.makedirs(os.path.join(args.output, 'weights'), exist_ok=True)
-    if args.logDispStep != -1 and not os.path.exists(os.path.join(args.output, 'disparities')):
+    if (args.logDispStep != -1 or args.dumpOutputs) and not os.path.exists(os.path.join(args.output, 'disparities')):
         os.makedirs(os.path.join(args.output, 'disparities'))
     shutil.copy(args.blockConfig, os.path.join(args.output, 'config.json'))
     with open(os.path.join(args.output, 'params.sh'), 'w+') as out:

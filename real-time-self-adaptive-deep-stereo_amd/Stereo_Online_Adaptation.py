@@ -75,7 +75,8 @@ def main(args):
     right_img_batch = torch.zeros(1, H, W, 3, device=dev)
     net_args = {'left_img': left_img_batch, 'right_img': right_img_batch, 'split_layers': [None], 'sequence': True,
                 'train_portion': 'BEGIN', 'bulkhead': True if args.mode == 'MAD' else False,
-                'weights': load_weights(args.weights, args.modelName, allow_missing=getattr(args, 'allowMissingWeights', False))}
+                'weights': load_weights(args.weights, args.modelName, allow_missing=getattr(args, 'allowMissingWeights', False)),
+                'precision': getattr(args, 'precision', 'fp32')}
     stereo_net = Nets.get_stereo_net(args.modelName, net_args)
     print('Stereo Prediction Model:\n', stereo_net)
     predictions = stereo_net.get_disparities()
@@ -162,7 +163,7 @@ def build_parser():
     parser.add_argument("--blockConfig", help="json file listing the layers of every trainable portion", required=True)
     parser.add_argument("--sampleMode", help="strategy that picks the portions to train", choices=sampler_factory.AVAILABLE_SAMPLER, default='SAMPLE')
     parser.add_argument("--fixedID", help="portion indices for --sampleMode FIXED", type=int, nargs='+', default=[0])
-    parser.add_argument("--reprojectionScale", help="losses at 1/scale resolution (only 1 is supported here)", default=1, type=int)
+    parser.add_argument("--reprojectionScale", help="MAD mode: the loss of a trained portion is computed on the frames and its prediction resized to 1/scale of the image size (bilinear, without half-pixel centres); the full-resolution loss and the metrics are unaffected; FULL / NONE ignore it", default=1, type=int)
     parser.add_argument("--summary", help="accepted for compatibility; no TensorBoard summaries are written", action='store_true')
     parser.add_argument("--imageShape", help="height width every frame is centre-cropped / zero-padded to", nargs='+', type=int, default=[320, 1216])
     parser.add_argument("--SSIMTh", help="restore the initial weights when the loss exceeds this value", type=float, default=0.5)
@@ -170,6 +171,7 @@ def build_parser():
     parser.add_argument("--mode", help="NONE = inference only, FULL = full back-propagation, MAD = modular adaptation", choices=['NONE', 'FULL', 'MAD'], default='MAD')
     parser.add_argument("--allowMissingWeights", help="variables absent from the checkpoint keep Xavier values (the reference's silent behaviour) instead of raising", action='store_true')
     parser.add_argument("--logDispStep", help="dump the disparity every K frames (-1: never)", default=-1, type=int)
+    parser.add_argument("--precision", help="MFMA arithmetic of the conv kernels: fp32 (default; the reference adapts in fp32), mixed (forward within fp32 tolerance, bf16 gradients) or bf16 (opt-in throughput mode)", choices=['fp32', 'mixed', 'bf16'], default='fp32')
     return parser
 
 

@@ -813,6 +813,141 @@ __global__ __launch_bounds__(256) void proxy_grad_kernel(ProxyArgs p) {
 }
 
 // ------------------------------------------------------------------------------------------
+// the MAD blocks' proxy loss at 1/s scale (Stereo_Continual_Adaptation.py:26-27,95-112 with --reprojectionScale s): the block's
+// full-size prediction and the proxy labels are both resized (TF1 legacy bilinear, interp1 / bilerp above) to Hs x Ws = H//s x W//s, the
+// proxy divided by s:   p = R(pred),  q = R(proxy) / s,  valid = !(q <= 0 || q >= 192),  loss = weight * sum(valid |p - q|) / sum(valid),
+//   d loss / d pred = grad_scale * weight * R^T(valid * sign(p - q)) / sum(valid)        on the full H x W grid.
+// Both maps are sampled on the fly -- launch 1 for the partial sums, launch 3 again per candidate output pixel of a source pixel (the gather
+// walk of resize_bwd_kernel, fixed order, no atomics, every element of dpred written); launch 2 is proxy_final_kernel.
+// ------------------------------------------------------------------------------------------
+struct ProxySArgs { const float* pred; const float* proxy; float* part; const float* result; float* dpred; int B, H, W, Hs, Ws; float sy, sx, fs, weight, gs; };
+
+// interp1 without mul+sub contraction: t is EXACTLY fl(i * scale) - lo.  Where fl(i * scale) is an integer (row 21 of 128 -> 42 rows: 21 * fl(128 / 42) rounds to 64) the
+// upper tap must carry the weight 0, not the 5e-7 an fma leaves behind: a label whose lower taps are holes (exactly 0) is then exactly 0 -- invalid -- in both launches
+// and in any other arithmetic that rounds the product first, instead of a tiny valid value in whichever launch the compiler happened to contract.
+__device__ __forceinline__ void interp1_exact(int i, float scale, int n, int& lo, int& hi, float& t) {
+#if defined(__clang__)
+#pragma clang fp contract(off)
+#endif
+    const float src = (float)i * scale;
+    lo = (int)src;
+    hi = min(lo + 1, n - 1);
+    t = src - (float)lo;
+}
+
+// p - q at one output pixel whose taps are given; v = its validity
+__device__ __forceinline__ float proxy_s_diff(const ProxySArgs& p, const float* pred, const float* proxy, int y0, int y1, float ty, int x0, int x1, float tx,
+                                              float& v) {
+    const float pv = bilerp(pred, p.W, y0, y1, ty, x0, x1, tx, 1.0f, false);
+    const float q = bilerp(proxy, p.W, y0, y1, ty, x0, x1, tx, 1.0f, false) / p.fs;
+    v = (q <= 0.f || q >= 192.0f) ? 0.f : 1.f;
+    return pv - q;
+}
+
+__global__ __launch_bounds__(256) void proxy_s_partial_kernel(ProxySArgs p) {
+    __shared__ float red[4];
+    const int64_t total = (int64_t)p.B * p.Hs * p.Ws;
+    const int64_t q = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    float e = 0.f, v = 0.f;
+    if (q < total) {
+        const int x = (int)(q % p.Ws);
+        const int64_t t2 = q / p.Ws;
+        const int y = (int)(t2 % p.Hs);
+        const int64_t off = (t2 / p.Hs) * p.H * p.W;
+        int y0, y1, x0, x1; float ty, tx;
+        interp1_exact(y, p.sy, p.H, y0, y1, ty);
+        interp1_exact(x, p.sx, p.W, x0, x1, tx);
+        e = fabsf(proxy_s_diff(p, p.pred + off, p.proxy + off, y0, y1, ty, x0, x1, tx, v)) * v;
+    }
+    const float se = block_sum(e, red);
+    const float sv = block_sum(v, red);
+    if (threadIdx.x == 0) { p.part[blockIdx.x * 2 + 0] = se; p.part[blockIdx.x * 2 + 1] = sv; }
+}
+
+// one lane per SOURCE pixel: the output pixels whose lower / upper tap is this pixel, rows outside, columns inside (resize_bwd_kernel's candidate window)
+__global__ __launch_bounds__(256) void proxy_s_grad_kernel(ProxySArgs p) {
+    const int64_t total = (int64_t)p.B * p.H * p.W;
+    const float isy = 1.0f / p.sy, isx = 1.0f / p.sx;
+    const float k = p.gs * p.weight;
+    const float nvalid = p.result[1];
+    for (int64_t q = (int64_t)blockIdx.x * 256 + threadIdx.x; q < total; q += (int64_t)gridDim.x * 256) {
+        const int sx = (int)(q % p.W);
+        const int64_t t2 = q / p.W;
+        const int sy = (int)(t2 % p.H);
+        const int64_t off = (t2 / p.H) * p.H * p.W;
+        const int ya = max(0, (int)floorf((float)(sy - 1) * isy) - 1), yb = min(p.Hs - 1, (int)ceilf((float)(sy + 1) * isy) + 1);
+        const int xa = max(0, (int)floorf((float)(sx - 1) * isx) - 1), xb = min(p.Ws - 1, (int)ceilf((float)(sx + 1) * isx) + 1);
+        float acc = 0.f;
+        for (int Y = ya; Y <= yb; ++Y) {
+            int y0, y1; float ty;
+            interp1_exact(Y, p.sy, p.H, y0, y1, ty);
+            const float wy = (y0 == sy ? 1.0f - ty : 0.f) + (y1 == sy ? ty : 0.f);
+            if (wy == 0.f) continue;
+            for (int X = xa; X <= xb; ++X) {
+                int x0, x1; float tx;
+                interp1_exact(X, p.sx, p.W, x0, x1, tx);
+                const float wx = (x0 == sx ? 1.0f - tx : 0.f) + (x1 == sx ? tx : 0.f);
+                if (wx == 0.f) continue;
+                float v;
+                const float d = proxy_s_diff(p, p.pred + off, p.proxy + off, y0, y1, ty, x0, x1, tx, v);
+                const float sgn = d > 0.f ? 1.f : (d < 0.f ? -1.f : 0.f);
+                acc += v * sgn * wy * wx;
+            }
+        }
+        p.dpred[q] = k * acc / nvalid;
+    }
+}
+
+// ------------------------------------------------------------------------------------------
+// KITTI D1-all and EPE of the continual loop (Stereo_Continual_Adaptation.py:245-249): val = gt > 0, diff = |gt - disp| on val,
+// outlier = diff > 3 && diff / gt >= 0.05.  The error sum of a workgroup is taken in double (the report prints three decimals of a mean
+// over ~4e5 pixels); counts are exact in float.
+// ------------------------------------------------------------------------------------------
+struct KittiArgs { const float* disp; const float* gt; float* part; float* result; int64_t total; int nblk; };
+
+__global__ __launch_bounds__(256) void metrics_kitti_kernel(KittiArgs p) {
+    __shared__ float red[4];
+    __shared__ double dred[256];
+    const int64_t q = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    float diff = 0.f, bad = 0.f, v = 0.f;
+    if (q < p.total) {
+        const float gt = p.gt[q];
+        if (gt > 0.f) {
+            v = 1.f;
+            diff = fabsf(gt - p.disp[q]);
+            bad = (diff > 3.0f && diff / gt >= 0.05f) ? 1.f : 0.f;
+        }
+    }
+    dred[threadIdx.x] = (double)diff;
+    __syncthreads();
+    for (int o = 128; o > 0; o >>= 1) { if ((int)threadIdx.x < o) dred[threadIdx.x] += dred[threadIdx.x + o]; __syncthreads(); }
+    const float sb = block_sum(bad, red);
+    const float sv = block_sum(v, red);
+    if (threadIdx.x == 0) { p.part[blockIdx.x * 3 + 0] = (float)dred[0]; p.part[blockIdx.x * 3 + 1] = sb; p.part[blockIdx.x * 3 + 2] = sv; }
+}
+
+__global__ __launch_bounds__(256) void metrics_kitti_final_kernel(KittiArgs p) {
+    __shared__ double red[3][256];
+    double a = 0, b = 0, c = 0;
+    for (int i = threadIdx.x; i < p.nblk; i += 256) { a += p.part[i * 3]; b += p.part[i * 3 + 1]; c += p.part[i * 3 + 2]; }
+    red[0][threadIdx.x] = a; red[1][threadIdx.x] = b; red[2][threadIdx.x] = c;
+    __syncthreads();
+    for (int o = 128; o > 0; o >>= 1) {
+        if ((int)threadIdx.x < o) {
+            red[0][threadIdx.x] += red[0][threadIdx.x + o];
+            red[1][threadIdx.x] += red[1][threadIdx.x + o];
+            red[2][threadIdx.x] += red[2][threadIdx.x + o];
+        }
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) {
+        p.result[0] = (float)(red[0][0] / red[2][0]);               // no valid pixel: 0/0 = NaN, like np.mean of an empty selection
+        p.result[1] = (float)(100.0 * (red[1][0] / red[2][0]));
+        p.result[2] = (float)red[2][0];
+    }
+}
+
+// ------------------------------------------------------------------------------------------
 // momentum / glue
 // ------------------------------------------------------------------------------------------
 // 16-byte form (all three buffers 16-byte aligned: the engines' flat buffers are): two loads in flight per lane, the launch sits behind the join
@@ -1214,6 +1349,42 @@ extern "C" int mh_supervised_loss(const float* pred, const float* target, float*
                                   float grad_scale, float max_disp, int32_t B, int32_t H, int32_t W, void* stream) {
     MH_REQUIRE(max_disp > 0.f, MH_ERR_ARG, "mh_supervised_loss: max_disp must be positive");
     return masked_l1("mh_supervised_loss", pred, target, ws, result, dpred, weight, grad_scale, max_disp, 1, B, H, W, stream);
+}
+
+extern "C" int64_t mh_proxy_scaled_ws_floats(int32_t B, int32_t H, int32_t W, int32_t scale) {
+    if (scale < 1) scale = 1;
+    return 2 * nblk((int64_t)B * (H / scale) * (W / scale));
+}
+
+extern "C" int mh_proxy_loss_scaled(const float* pred, const float* proxy, float* ws, float* result, float* dpred, float weight,
+                                    float grad_scale, int32_t scale, int32_t B, int32_t H, int32_t W, void* stream) {
+    MH_REQUIRE(pred && proxy && ws && result, MH_ERR_ARG, "mh_proxy_loss_scaled: null argument");
+    MH_REQUIRE(B > 0 && H > 0 && W > 0 && H < 65536 && W < 65536, MH_ERR_ARG, "mh_proxy_loss_scaled: bad dimension");
+    MH_REQUIRE(scale >= 1 && scale <= H && scale <= W, MH_ERR_ARG, "mh_proxy_loss_scaled: scale must lie in 1 .. min(H, W)");
+    const int Hs = H / scale, Ws = W / scale;
+    const int64_t nout = (int64_t)B * Hs * Ws;
+    MH_REQUIRE((int64_t)B * H * W < (1ll << 31), MH_ERR_ARG, "mh_proxy_loss_scaled: too many pixels");
+    ProxySArgs a{pred, proxy, ws, result, dpred, B, H, W, Hs, Ws, (float)H / (float)Hs, (float)W / (float)Ws, (float)scale, weight, grad_scale};
+    ProxyArgs f{};                                                     // (the final reduction is the un-scaled loss's)
+    f.part = ws; f.result = result; f.nblk = (int)nblk(nout); f.weight = weight;
+    hipStream_t s = (hipStream_t)stream;
+    hipLaunchKernelGGL(proxy_s_partial_kernel, dim3(f.nblk), dim3(256), 0, s, a);
+    hipLaunchKernelGGL(proxy_final_kernel, dim3(1), dim3(256), 0, s, f);
+    if (dpred) hipLaunchKernelGGL(proxy_s_grad_kernel, dim3(grid_for((int64_t)B * H * W)), dim3(256), 0, s, a);
+    return mh_check_launch("mh_proxy_loss_scaled");
+}
+
+extern "C" int64_t mh_metrics_kitti_ws_floats(int32_t B, int32_t H, int32_t W) { return 3 * nblk((int64_t)B * H * W) + 16; }
+
+extern "C" int mh_metrics_kitti(const float* disp, const float* gt, float* ws, float* result, int32_t B, int32_t H, int32_t W, void* stream) {
+    MH_REQUIRE(disp && gt && ws && result, MH_ERR_ARG, "mh_metrics_kitti: null argument");
+    MH_REQUIRE(B > 0 && H > 0 && W > 0, MH_ERR_ARG, "mh_metrics_kitti: bad dimension");
+    MH_REQUIRE((int64_t)B * H * W < (1ll << 31), MH_ERR_ARG, "mh_metrics_kitti: too many pixels");
+    KittiArgs a{disp, gt, ws, result, (int64_t)B * H * W, (int)nblk((int64_t)B * H * W)};
+    hipStream_t s = (hipStream_t)stream;
+    hipLaunchKernelGGL(metrics_kitti_kernel, dim3(a.nblk), dim3(256), 0, s, a);
+    hipLaunchKernelGGL(metrics_kitti_final_kernel, dim3(1), dim3(256), 0, s, a);
+    return mh_check_launch("mh_metrics_kitti");
 }
 
 extern "C" int mh_adam(float* var, float* m, float* v, const float* grad, int64_t n, const float* state, float lr, float beta1,

@@ -31,7 +31,8 @@ class Op(C.Structure):
 (OP_CONV, OP_WGRAD, OP_CORR_FWD, OP_CORR_BWD, OP_WARP_FWD, OP_WARP_BWD, OP_RESIZE_FWD, OP_RESIZE_BWD,
  OP_PAD_REFLECT, OP_LOSS, OP_METRICS, OP_MOMENTUM, OP_COPY_CH, OP_LEAKY_BWD, OP_FILL, OP_BIAS_GRAD,
  OP_WGRAD_PARTIAL, OP_WGRAD_REDUCE, OP_PROXY_LOSS, OP_SUPERVISED_LOSS, OP_ADAM, OP_ADAM_ADVANCE, OP_RESIZE_IMAGE, OP_LEVEL_FRONT, OP_RESERVED_25, OP_PACK_W, OP_CORR_WARP_BWD,
- OP_SHADOW_CAST, OP_WGRAD_STREAM, OP_HEAD_BWD, OP_HEAD_FWD, OP_CONV_PLANES, OP_PLANE_SPLIT, OP_STAMP, OP_CONV_PLANES_BWD, OP_DET_FLUSH, OP_CONV_IMAGE, OP_ALLREDUCE, OP_FETCH_INPUTS) = range(1, 40)
+ OP_SHADOW_CAST, OP_WGRAD_STREAM, OP_HEAD_BWD, OP_HEAD_FWD, OP_CONV_PLANES, OP_PLANE_SPLIT, OP_STAMP, OP_CONV_PLANES_BWD, OP_DET_FLUSH, OP_CONV_IMAGE, OP_ALLREDUCE, OP_FETCH_INPUTS,
+ OP_PROXY_LOSS_SCALED, OP_METRICS_KITTI) = range(1, 42)
 
 
 COMM_ID_BYTES = 128            # MH_COMM_ID_BYTES
@@ -146,6 +147,8 @@ SIGNATURES = {
     "mh_tune_wgrad_stream": (_I, [_I]),
     "mh_proxy_ws_floats": (_L, [_I, _I, _I]),
     "mh_proxy_loss": (_I, [_P, _P, _P, _P, _P, _F, _F, _I, _I, _I, _P]),
+    "mh_proxy_scaled_ws_floats": (_L, [_I, _I, _I, _I]),
+    "mh_proxy_loss_scaled": (_I, [_P, _P, _P, _P, _P, _F, _F, _I, _I, _I, _I, _P]),
     "mh_supervised_loss": (_I, [_P, _P, _P, _P, _P, _F, _F, _F, _I, _I, _I, _P]),
     "mh_adam": (_I, [_P, _P, _P, _P, _L, _P, _F, _F, _F, _F, _F, _P]),
     "mh_adam_advance": (_I, [_P, _F, _F, _P]),
@@ -173,6 +176,8 @@ SIGNATURES = {
     "mh_reprojection_loss_phase": (_I, [_P, _P, _P, _P, _P, _P, _F, _I, _I, _I, _I, _P]),
     "mh_metrics_ws_floats": (_L, [_I, _I, _I]),
     "mh_metrics": (_I, [_P, _P, _P, _P, _F, _I, _I, _I, _P]),
+    "mh_metrics_kitti_ws_floats": (_L, [_I, _I, _I]),
+    "mh_metrics_kitti": (_I, [_P, _P, _P, _P, _I, _I, _I, _P]),
     "mh_momentum": (_I, [_P, _P, _P, _L, _F, _F, _F, _P]),
     "mh_copy_channels": (_I, [_P, _I, _P, _I, _L, _I, _F, _I, _P]),
     "mh_leaky_bwd": (_I, [_P, _I, _P, _I, _L, _I, _F, _P]),
@@ -204,7 +209,7 @@ SIGNATURES = {
     "mh_event_destroy": (_I, [_P]),
     "mh_stream_sync": (_I, [_P]),
 }
-_NO_STATUS = {"mh_comm_available", "mh_deterministic_overflow", "mh_bias_grad_blocks", "mh_tune_conv_bank_small", "mh_conv_image_ok", "mh_level_front_head_ok", "mh_deterministic_ranges", "mh_planes_kc16", "mh_conv2d_planes_bwd_ok", "mh_stamp_rate_khz", "mh_pack32_bytes", "mh_conv2d_planes_ok", "mh_tune_conv_planes", "mh_tune_wgrad_target_pct", "mh_tune_wgrad_image", "mh_conv2d_takes_shadows", "mh_tune_conv_bank_tile", "mh_tune_conv_rows", "mh_last_error", "mh_last_kernel", "mh_tune_conv_bank", "mh_pack_bytes", "mh_abi_version", "mh_tune_conv_patch", "mh_crc32c", "mh_device_count", "mh_loss_ws_floats", "mh_metrics_ws_floats", "mh_proxy_ws_floats"}
+_NO_STATUS = {"mh_comm_available", "mh_deterministic_overflow", "mh_bias_grad_blocks", "mh_tune_conv_bank_small", "mh_conv_image_ok", "mh_level_front_head_ok", "mh_deterministic_ranges", "mh_planes_kc16", "mh_conv2d_planes_bwd_ok", "mh_stamp_rate_khz", "mh_pack32_bytes", "mh_conv2d_planes_ok", "mh_tune_conv_planes", "mh_tune_wgrad_target_pct", "mh_tune_wgrad_image", "mh_conv2d_takes_shadows", "mh_tune_conv_bank_tile", "mh_tune_conv_rows", "mh_last_error", "mh_last_kernel", "mh_tune_conv_bank", "mh_pack_bytes", "mh_abi_version", "mh_tune_conv_patch", "mh_crc32c", "mh_device_count", "mh_loss_ws_floats", "mh_metrics_ws_floats", "mh_proxy_ws_floats", "mh_proxy_scaled_ws_floats", "mh_metrics_kitti_ws_floats"}
 
 
 class MadnetHipError(RuntimeError):

@@ -33,13 +33,16 @@ class Adapter(object):
     def __init__(self, net, mode="MAD", block_config=None, lr=1e-4, momentum=0.9, sample_mode="PROBABILITY",
                  num_blocks=1, fixed_id=0, sample_frequency=1, ssim_th=0.5, reprojection_scale=1,
                  use_graph=True, shared_model=False, process_group=None, loss="reprojection", dilation=1, decay=0.99, uf=0.01,
-                 optimizer="momentum", reset_optimizer=False, reward_every_step_first=False, early_reduce=None, in_graph_collective=None, fetch_inputs=None):
+                 optimizer="momentum", reset_optimizer=False, reward_every_step_first=False, early_reduce=None, in_graph_collective=None, fetch_inputs=None,
+                 kitti_metrics=False):
         """loss='proxy', dilation, decay, uf: the continual-adaptation variant (Stereo_Continual_Adaptation.py:75-112,
         205-249, 302-304): proxy-label mean_l1 loss, weight update only every `dilation`-th frame, reward update
         sample_distribution = decay * sample_distribution (+ uf * gain on the last trained blocks).
         optimizer='adam', reset_optimizer, reward_every_step_first: the live demo's variant of the loop (Demo/demo_model.py:164,
         203-208, 253-262): tf.train.AdamOptimizer(lr) instead of momentum; a reset without a weight file re-runs the initialisers,
-        i.e. also clears the optimizer slots; its `first` flag is never cleared, so every step re-seeds both remembered losses."""
+        i.e. also clears the optimizer slots; its `first` flag is never cleared, so every step re-seeds both remembered losses.
+        kitti_metrics: the step also computes the continual loop's report (Stereo_Continual_Adaptation.py:245-249) -- EPE over gt > 0 and KITTI D1-all -- as one more
+        op of its plan (mh_metrics_kitti); step() then returns them as out['epe_gt0'] / out['d1'].  False: every plan is what it is without the keyword."""
         if optimizer not in ("momentum", "adam"):
             raise ValueError("optimizer must be 'momentum' or 'adam'")
         self.optimizer, self.reset_optimizer, self.reward_every_step_first = optimizer, reset_optimizer, reward_every_step_first
@@ -51,8 +54,11 @@ class Adapter(object):
         self.loss, self.dilation, self.decay, self.uf = loss, max(1, int(dilation)), decay, uf
         if loss == "proxy":
             if not hasattr(self.eng, "proxy"):
-                raise NotImplementedError("the proxy-label loss is implemented for the MADNet engine")
+                raise NotImplementedError("the proxy-label loss needs an engine with a proxy buffer")
             self.eng.loss_kind = "proxy"
+        self.kitti = bool(kitti_metrics)
+        if self.kitti:
+            self.eng.kitti_metrics = True
         if reprojection_scale != 1:
             # only the MAD blocks' losses use the scaled inputs (Stereo_Online_Adaptation.py:91-107); FULL / NONE ignore the flag
             if mode == "MAD":
@@ -116,7 +122,9 @@ class Adapter(object):
         self._plans = {}
         self._coll_buf = None          # staging buffer of the MAD shared-model collective (step)
         self.eng.params.w0 = self.eng.params.w.clone()              # restore target (initial weights)
-        self._host = torch.zeros(8, pin_memory=self.cuda)
+        # pinned read-back buffer: [loss result (4) | EPE / bad3 (4)], with kitti_metrics [loss result (4) | KITTI report (4) | EPE / bad3 (4)]
+        self._host = torch.zeros(12 if self.kitti else 8, pin_memory=self.cuda)
+        self._o_met = 8 if self.kitti else 4
 
     # -------------------------------------------------------------------------------------------
     def _plan(self, key):
@@ -187,8 +195,11 @@ class Adapter(object):
 
     def _readback(self):
         """results -> the pinned host buffer (on the CURRENT stream)"""
-        self._host[0:4].copy_(self.eng.res_loss, non_blocking=True)
-        self._host[4:8].copy_(self.eng.res_met, non_blocking=True)
+        if self.kitti:             # the report sits right behind the loss result (params.Params): one transfer carries both
+            self._host[0:8].copy_(self.eng.params.loss_kitti, non_blocking=True)
+        else:
+            self._host[0:4].copy_(self.eng.res_loss, non_blocking=True)
+        self._host[self._o_met:self._o_met + 4].copy_(self.eng.res_met, non_blocking=True)
 
     def step(self, left, right, gt=None, proxy=None):
         eng = self.eng
@@ -251,7 +262,7 @@ class Adapter(object):
         """host side of a step whose results sit in the pinned buffer: reward update, reset check, bookkeeping"""
         eng = self.eng
         new_loss = float(self._host[0]) / (self.world if self.shared else 1)
-        epe = float(self._host[4]); bad3 = float(self._host[5])
+        epe = float(self._host[self._o_met]); bad3 = float(self._host[self._o_met + 1])
         # ---- reward update of the sampling logits (Stereo_Online_Adaptation.py:211-224)
         if self.mode == "MAD":
             if self.step_count == 0 or self.reward_every_step_first:
@@ -280,8 +291,11 @@ class Adapter(object):
             self.reset_counter += 1
             did_reset = True
         self.step_count += 1
-        return {"epe": epe, "bad3": bad3, "loss": new_loss, "disparity": eng.pred,
-                "blocks": list(self.blocks_to_train) if self.mode == "MAD" else [], "reset": did_reset}
+        out = {"epe": epe, "bad3": bad3, "loss": new_loss, "disparity": eng.pred,
+               "blocks": list(self.blocks_to_train) if self.mode == "MAD" else [], "reset": did_reset}
+        if self.kitti:
+            out["epe_gt0"], out["d1"] = float(self._host[4]), float(self._host[5])
+        return out
 
 
 class MultiAdapter(object):

@@ -30,6 +30,8 @@ class EngineBase(object):
         self.images = Bf16Images(device)
         # deterministic test mode (Schedule.DETERMINISTIC): float atomics accumulate into 64-bit fixed-point twins the plan flushes in front of their readers
         self.deterministic = schedule.DETERMINISTIC
+        self.kitti_metrics = False                         # record mh_metrics_kitti next to mh_metrics (Adapter(kitti_metrics=True))
+        self.res_kitti = self.params.res_kitti
         self._det_bases = []
 
     def _det_twins(self, *bases):
@@ -62,6 +64,15 @@ class EngineBase(object):
             if src is not None:
                 dst = getattr(self, name)
                 dst.copy_(torch.as_tensor(src, dtype=torch.float32).reshape(dst.shape))
+
+    def record_metrics(self, r):
+        """EPE / bad3 of the step's disparity (Stereo_Online_Adaptation.py:74-82) and, with kitti_metrics, the continual loop's report -- EPE over gt > 0 and
+        KITTI D1-all (Stereo_Continual_Adaptation.py:245-249) -- on the same lane, into params.res_kitti"""
+        ops.metrics(r, self.pred, self.gt, self.met_ws, self.res_met, 3.0)
+        if self.kitti_metrics:
+            if getattr(self, "kitti_ws", None) is None:
+                self.kitti_ws = torch.zeros(self.lib.metrics_kitti_ws_floats(self.B, self.H0, self.W0), device=self.dev)
+            ops.metrics_kitti(r, self.pred, self.gt, self.kitti_ws, self.res_kitti)
 
     def _ensure_adam(self):
         """second Adam moment + the beta powers, on first use; True: created by this call (the caller adds its own training buffers)"""

@@ -274,6 +274,8 @@ OP_KERNEL_NAMES = {
     "OP_PACK_W": "pack_weights_kernel (MFMA fragment banks of every layer, once per step)", "OP_SHADOW_CAST": "shadow_cast_kernel (bf16 shadows of a filter-gradient batch)",
     "OP_HEAD_BWD": "head_bwd_kernel (disparity head: output gradient + 3x3 Cin->1 input gradient)", "OP_HEAD_FWD": "conv_n1_fwd_kernel (disparity head with extra destinations)",
     "OP_PLANE_SPLIT": "plane_split_kernel (hi / lo bf16 planes + fused concat)", "OP_STAMP": "stamp_kernel", "OP_DET_FLUSH": "det_flush_kernel",
+    "OP_PROXY_LOSS_SCALED": "proxy_s_partial_kernel + proxy_final_kernel + proxy_s_grad_kernel (a MAD block's proxy loss at 1/s scale, both maps resized on the fly)",
+    "OP_METRICS_KITTI": "metrics_kitti_kernel + metrics_kitti_final_kernel (EPE over gt > 0 / D1-all)",
 }
 _REPORTING = ("OP_CONV", "OP_WGRAD", "OP_WGRAD_PARTIAL", "OP_WGRAD_STREAM", "OP_CORR_FWD", "OP_CORR_BWD", "OP_LEVEL_FRONT", "OP_CORR_WARP_BWD", "OP_CONV_PLANES", "OP_CONV_IMAGE",
               "OP_CONV_PLANES_BWD")

@@ -100,6 +100,9 @@ class DispNetEngine(EngineBase):
         z = lambda *s: torch.zeros(*s, device=device)
         self.left = z(B, H, W, 3); self.right = z(B, H, W, 3); self.gt = z(B, H, W)
         self.pred = z(B, H, W); self.dpred = z(B, H, W)
+        # continual-adaptation variant (loss_kind = 'proxy'): proxy labels + the mean_l1 loss workspace
+        self.proxy = z(B, H, W); self.proxy_ws = z(lib.proxy_ws_floats(B, H, W))
+        self.loss_kind = "reprojection"
         self.loss_ws = z(lib.loss_ws_floats(B, H, W)); self.met_ws = z(lib.metrics_ws_floats(B, H, W))
         self.res_loss = self.params.g_loss[self.params.total:self.params.total + 4]; self.res_met = z(4)   # (loss result behind the gradients: one collective carries both)
         self.ops = []
@@ -352,8 +355,15 @@ class DispNetEngine(EngineBase):
                        mul=float(self.Wp) / float(n.st.W), mode=1)
 
     def record_loss_metrics(self, r, with_grad):
-        ops.reprojection_loss(r, self.left, self.right, self.pred, self.loss_ws, self.res_loss, self.dpred if with_grad else None)
-        ops.metrics(r, self.pred, self.gt, self.met_ws, self.res_met, 3.0)
+        """full-resolution reprojection loss -- or, loss_kind 'proxy', full_proxy_loss of the continual variant (Stereo_Continual_Adaptation.py:75: mean_l1 against the
+        proxy labels, weight 0.01; of the reduced multi-scale sum only the last prediction contributes) -- + EPE / bad3"""
+        if self.loss_kind not in ("reprojection", "proxy"):
+            raise ValueError("loss_kind must be 'reprojection' or 'proxy'")
+        if self.loss_kind == "proxy":
+            ops.proxy_loss(r, self.pred, self.proxy, self.proxy_ws, self.res_loss, self.dpred if with_grad else None, weight=0.01)
+        else:
+            ops.reprojection_loss(r, self.left, self.right, self.pred, self.loss_ws, self.res_loss, self.dpred if with_grad else None)
+        self.record_metrics(r)
 
     # ---- backward (derived from the op list) ------------------------------------------------------------
     def _contribute(self, node):
@@ -573,7 +583,7 @@ class DispNetEngine(EngineBase):
                 ops.supervised_loss(r, self.disp_ms[name], self.gt, self.sup_ws, self.res_loss_ms[i + 1], self.ddisp_ms[name],
                                     weight=lw[i + 1], max_disp=max_disp)
                 heads.append((self.prediction if name == "prediction" else self.predict[name], self.ddisp_ms[name]))
-            ops.metrics(r, self.pred, self.gt, self.met_ws, self.res_met, 3.0)
+            self.record_metrics(r)
             self.record_backward(r, heads=heads)
         if update and part in ("all", "update"):
             self.record_adam_all(r, lr, grad_scale)
@@ -581,10 +591,10 @@ class DispNetEngine(EngineBase):
 
     def build_plan(self, mode, lr=1e-4, grad_scale=1.0, update=True, part="all", loss_weights=None, max_disp=192.0,
                    optimizer="momentum", momentum=0.9, inputs=None, **_):
-        """inputs: an ops.InputTable -- the plan's first op fills left / right / gt from the device tensors the table names (engine.MadNetEngine.build_plan)"""
+        """inputs: an ops.InputTable -- the plan's first op fills left / right / gt / proxy from the device tensors the table names (engine.MadNetEngine.build_plan)"""
         r = Recorder()
         if inputs is not None and part != "update":
-            ops.fetch_inputs(r, inputs.ptr, [self.left, self.right, self.gt])
+            ops.fetch_inputs(r, inputs.ptr, [self.left, self.right, self.gt] + ([self.proxy] if self.loss_kind == "proxy" else []))
         r.wgrad_group_max_m = 0      # per-plan cap of the grouped filter gradients (0 = library default; 4096 and 16384 measure the same here)
         self.wsa.reset()
         # DispNet's filter gradients (few pixels, 256-1024 channels) keep the round-1 pixel-split targets: 3.99 vs 4.08 ms (the split counts are resolved

@@ -150,13 +150,26 @@ class MadNetEngine(EngineBase, ElisionPasses, BackwardRecorder):
         if s < 1:
             raise ValueError("reprojectionScale must be >= 1")
         self.rscale = s
-        if s != 1:
-            B, Hs, Ws = self.B, self.H0 // s, self.W0 // s
-            z = self._buf
+        self._scale_bufs = None
+        self._ensure_scale_buffers()
+        self._plans = {}
+
+    def _ensure_scale_buffers(self):
+        """what the MAD blocks' loss at 1/rscale needs, for the current loss_kind.  Reprojection: the resized frames, the resized prediction and its gradient,
+        the loss workspace at that size.  Proxy (Stereo_Continual_Adaptation.py:95-112: proxy labels resized too and divided by the scale): ONE workspace --
+        mh_proxy_loss_scaled samples the prediction and the labels on the fly, no resized map exists."""
+        s = self.rscale
+        if s == 1 or getattr(self, "_scale_bufs", None) == (s, self.loss_kind):
+            return
+        B, Hs, Ws = self.B, self.H0 // s, self.W0 // s
+        z = self._buf
+        if self.loss_kind == "proxy":
+            self.proxy_ws_s = z(self.lib.proxy_scaled_ws_floats(B, self.H0, self.W0, s))
+        else:
             self.left_s = z(B, Hs, Ws, 3); self.right_s = z(B, Hs, Ws, 3)
             self.p_s = z(B, Hs, Ws); self.dp_s = z(B, Hs, Ws)
             self.loss_ws_s = z(self.lib.loss_ws_floats(B, Hs, Ws))
-        self._plans = {}
+        self._scale_bufs = (s, self.loss_kind)
 
     # views -----------------------------------------------------------------------------------
     def _fv(self, t):
@@ -515,11 +528,11 @@ class MadNetEngine(EngineBase, ElisionPasses, BackwardRecorder):
                 self._flush_x0(r)               # (the padded frames: read by conv1's filter gradient only, on this lane, at the far end of the step)
                 if self.loss_kind != "proxy":
                     ops.reprojection_loss(r, self.left, self.right, self.pred, self.loss_ws, self.res_loss, None, phase=2)
-                ops.metrics(r, self.pred, self.gt, self.met_ws, self.res_met, 3.0)
+                self.record_metrics(r)
             finally:
                 r.lane = 0
         else:
-            ops.metrics(r, self.pred, self.gt, self.met_ws, self.res_met, 3.0)
+            self.record_metrics(r)
 
     # =========================================================================================
     # backward
@@ -639,7 +652,7 @@ class MadNetEngine(EngineBase, ElisionPasses, BackwardRecorder):
                 gbuf = self.dpred if hd == "final" else self.ddisp_ms[hd]
                 ops.supervised_loss(r, pred, self.gt, self.sup_ws, self.res_loss_ms[i], gbuf, weight=lw[i], max_disp=max_disp)
                 heads[hd] = gbuf
-            ops.metrics(r, self.pred, self.gt, self.met_ws, self.res_met, 3.0)
+            self.record_metrics(r)
             self.record_backward(r, None, tv, bulkhead=False, heads=heads)
         if update and part in ("all", "update"):
             self.record_update_adam(r, tv, lr, grad_scale=grad_scale)
@@ -721,15 +734,18 @@ class MadNetEngine(EngineBase, ElisionPasses, BackwardRecorder):
                 self.record_forward(r, make_disps=tuple(lv for lv, _ in blocks))
                 self.record_loss_metrics(r, with_grad=False)
             if do_grad and self.rscale != 1:
-                if self.loss_kind == "proxy":
-                    raise NotImplementedError("reprojectionScale != 1 is implemented for the reprojection loss (the online script)")
-                ops.resize_image(r, self.left, self.left_s)           # inputs_modules (Stereo_Online_Adaptation.py:91-95)
-                ops.resize_image(r, self.right, self.right_s)
+                self._ensure_scale_buffers()
+                if self.loss_kind != "proxy":                         # (the proxy loss reads no frame: nothing to resize)
+                    ops.resize_image(r, self.left, self.left_s)       # inputs_modules (Stereo_Online_Adaptation.py:91-95)
+                    ops.resize_image(r, self.right, self.right_s)
             for nb, (lv, bv) in enumerate(blocks):
                 if do_grad:
                     # loss of the block's prediction: reprojection (Stereo_Online_Adaptation.py:98-107) or, continual
                     # variant, proxy-label mean_l1 with weight 0.1 (Stereo_Continual_Adaptation.py:100-112)
-                    if self.loss_kind == "proxy":
+                    if self.loss_kind == "proxy" and self.rscale != 1:
+                        # prediction and labels at 1/s scale, labels / s (:95-112), resized inside the op
+                        ops.proxy_loss_scaled(r, self.disp_k[lv], self.proxy, self.proxy_ws_s, self.res_loss_k, self.rscale, self.ddisp_k, weight=0.1)
+                    elif self.loss_kind == "proxy":
                         ops.proxy_loss(r, self.disp_k[lv], self.proxy, self.proxy_ws, self.res_loss_k, self.ddisp_k, weight=0.1)
                     elif self.rscale != 1:
                         Hs, Ws = self.H0 // self.rscale, self.W0 // self.rscale

@@ -758,6 +758,13 @@ def proxy_loss(lib, pred, proxy, ws, result, dpred=None, weight=0.01, grad_scale
     lib.proxy_loss(_p(pred), _p(proxy), _p(ws), _p(result), _p(dpred), weight, grad_scale, B, H, W, _p(stream))
 
 
+def proxy_loss_scaled(lib, pred, proxy, ws, result, scale, dpred=None, weight=0.1, grad_scale=1.0, stream=None):
+    """proxy_loss of the prediction and the proxy labels both resized to (H // scale, W // scale), the labels divided by scale (a MAD block's loss under
+    --reprojectionScale, Stereo_Continual_Adaptation.py:95-112) in one op; dpred = its gradient on the full-size grid (optional).  ws: proxy_scaled_ws_floats."""
+    B, H, W = pred.shape[0], pred.shape[1], pred.shape[2]
+    lib.proxy_loss_scaled(_p(pred), _p(proxy), _p(ws), _p(result), _p(dpred), weight, grad_scale, int(scale), B, H, W, _p(stream))
+
+
 def supervised_loss(lib, pred, target, ws, result, dpred=None, weight=1.0, grad_scale=1.0, max_disp=192.0, stream=None):
     """result[0] = weight * mean_l1(pred, target, valid = !(target == 0 | target >= max_disp)) -- one scale of
     loss_factory.get_supervised_loss (Train.py:100); dpred = its gradient (optional).  Workspace as proxy_loss."""
@@ -777,6 +784,12 @@ def adam_advance(lib, state, beta1=0.9, beta2=0.999, stream=None):
 def metrics(lib, disp, gt, ws, result, pixel_th=3.0, stream=None):
     B, H, W = disp.shape[0], disp.shape[1], disp.shape[2]
     lib.metrics(_p(disp), _p(gt), _p(ws), _p(result), pixel_th, B, H, W, _p(stream))
+
+
+def metrics_kitti(lib, disp, gt, ws, result, stream=None):
+    """result = [EPE over gt > 0, KITTI D1-all in percent, #valid] (Stereo_Continual_Adaptation.py:245-249)"""
+    B, H, W = disp.shape[0], disp.shape[1], disp.shape[2]
+    lib.metrics_kitti(_p(disp), _p(gt), _p(ws), _p(result), B, H, W, _p(stream))
 
 
 def momentum(lib, var, accum, grad, lr, mom=0.9, grad_scale=1.0, n=None, stream=None):

@@ -18,8 +18,12 @@ class Params(object):
         self.m = torch.zeros(off, device=device)
         # + 4 floats behind the gradients: the step's loss result lives there, so the shared-model mode all-reduces the
         # gradients AND the loss that drives the reward / reset logic with ONE collective (adapter.py)
-        self.g_loss = torch.zeros(off + 4, device=device)     # [gradients | loss result (4 floats)]
+        # + 4 more behind the loss: the KITTI report of the continual loop (mh_metrics_kitti), so that loss and report reach the host in one transfer
+        store = torch.zeros(off + 8, device=device)
+        self.g_loss = store[:off + 4]                          # [gradients | loss result (4 floats)]
         self.g = self.g_loss[:off]
+        self.res_kitti = store[off + 4:off + 8]                # [EPE over gt > 0, D1-all, #valid, -]
+        self.loss_kitti = store[off:off + 8]                   # loss result + report, contiguous
         self.w0 = None                                         # reset copy (restore target)
 
     def numel(self, name):

@@ -247,6 +247,9 @@ class Recorder(object):
     def proxy_loss(self, pred, proxy, ws, result, dpred, weight, grad_scale, B, H, W, stream):
         self._op(_ffi.OP_PROXY_LOSS, [B, H, W], [weight, grad_scale], [pred, proxy, ws, result, dpred])
 
+    def proxy_loss_scaled(self, pred, proxy, ws, result, dpred, weight, grad_scale, scale, B, H, W, stream):
+        self._op(_ffi.OP_PROXY_LOSS_SCALED, [B, H, W, scale], [weight, grad_scale], [pred, proxy, ws, result, dpred])
+
     def supervised_loss(self, pred, target, ws, result, dpred, weight, grad_scale, max_disp, B, H, W, stream):
         self._op(_ffi.OP_SUPERVISED_LOSS, [B, H, W], [weight, grad_scale, max_disp], [pred, target, ws, result, dpred])
 
@@ -259,6 +262,9 @@ class Recorder(object):
 
     def metrics(self, disp, gt, ws, result, th, B, H, W, stream):
         self._op(_ffi.OP_METRICS, [B, H, W], [th], [disp, gt, ws, result])
+
+    def metrics_kitti(self, disp, gt, ws, result, B, H, W, stream):
+        self._op(_ffi.OP_METRICS_KITTI, [B, H, W], [], [disp, gt, ws, result])
 
     def momentum(self, var, accum, grad, n, lr, mom, gs, stream):
         self._op(_ffi.OP_MOMENTUM, [], [lr, mom, gs], [var, accum, grad], n=n)
