@@ -148,23 +148,8 @@ extern "C" int mh_device_count(void) {
 }
 
 // ---- plan executor ------------------------------------------------------------------------
-// Field packing of mh_op per kind (host side: madnet_hip/plan.py must match):
-//  CONV      i[0..18] = mh_conv_desc ints in declaration order, i[19]=mask_c0 i[20]=mask_c1 i[22]=precision, f[0]=alpha f[1]=mask_alpha
-//            p[0]=in p[1]=w p[2]=bias p[3]=out p[4]=mask_ref
-//  WGRAD     same desc; i[21]=dout_ld ; p[0]=in p[1]=dout p[2]=dw p[3]=db
-//  CORR_FWD  i: l_ld r_ld out_ld coff B H W C md stride copy_left zero_tail ; p: L R u out
-//  CORR_BWD  i: g_ld coff l_ld r_ld dl_ld acc_l dr_ld acc_r acc_u B H W C md stride copy_left precision ; p: g L R dL dR du
-//  WARP_FWD  i: img_ld out_ld B H W C ; p: img u out
-//  WARP_BWD  i: g_ld img_ld dimg_ld acc_u B H W C ; p: g img u dimg du
-//  RESIZE_*  i: B Hi Wi Hr Wr cy cx Ho Wo mode accumulate ; f[0]=mul ; FWD p: in out ; BWD p: g in din
-//  PAD       i: B H W C Hp Wp pt pl out_ld ; f: div sub ; p: in out
-//  LOSS      i: B H W ; f[0]=grad_scale ; p: left right disp ws result ddisp
-//  METRICS   i: B H W ; f[0]=pixel_th ; p: disp gt ws result
-//  MOMENTUM  n ; f: lr momentum grad_scale ; p: var accum grad
-//  COPY_CH   i: src_ld dst_ld nch accumulate ; n=npix ; f[0]=scale ; p: src dst
-//  LEAKY_BWD i: dy_ld y_ld nch ; n=npix ; f[0]=alpha ; p: dy y
-//  FILL      n ; f[0]=v ; p: ptr
-//  BIAS_GRAD i: dz_ld nch ; n=npix ; p: dz db
+// Which value sits in which slot of mh_op, per kind, is stated in madnet_hip/oplayout.py (the host packs and reads through that table);
+// run_op() below reads the slots back in the argument order of the mh_* entry points.
 static void desc_from_op(const mh_op& o, mh_conv_desc& d) {
     const int32_t* i = o.i;
     d.B = i[0]; d.Hi = i[1]; d.Wi = i[2]; d.Ho = i[3]; d.Wo = i[4]; d.K = i[5]; d.N = i[6];
@@ -173,17 +158,30 @@ static void desc_from_op(const mh_op& o, mh_conv_desc& d) {
     d.alpha = o.f[0]; d.mask_alpha = o.f[1]; d.mask_c0 = i[19]; d.mask_c1 = i[20]; d.precision = i[22];
 }
 
+// MH_OP_CONV's flag word i[23] (oplayout.py: CONV_*; not the MH_CONV_* flags of mh_conv2d_sh3, which run_op derives from it)
+enum {
+    OPC_IN_SHADOW = 1,          // p[5] = bf16 shadow of the input
+    OPC_MASK_SHADOW = 2,        // p[2] = bf16 shadow of the mask (else the bias)
+    OPC_SHADOW_ONLY = 4,        // -> MH_CONV_SHADOW_ONLY
+    OPC_IN_F32_STALE = 8,       // -> MH_CONV_IN_F32_STALE
+    OPC_MASK_F32_STALE = 16,    // -> MH_CONV_MASK_F32_STALE
+    OPC_OUT_PLANES = 32,        // p[7] / p[5] = hi / lo planes of the result (mh_conv2d_sh4)
+};
+
 static int run_op(const mh_op& o, void* s) {
     const int32_t* i = o.i;
     void* const* p = o.p;
     switch (o.kind) {
         case MH_OP_CONV: {
             mh_conv_desc d; desc_from_op(o, d);
-            if (i[23] & 32) return mh_conv2d_sh4(&d, (const float*)p[0], (const float*)p[1], p[6], (const float*)p[2], (float*)p[3], (const float*)p[4], p[7], p[5], s);
-            if (i[23] & 30) return mh_conv2d_sh3(&d, (const float*)p[0], (i[23] & 1) ? p[5] : nullptr, (const float*)p[1], p[6], nullptr, (float*)p[3], (const float*)p[4],
-                                              (i[23] & 2) ? p[2] : nullptr, p[7],
-                                              ((i[23] & 4) ? MH_CONV_SHADOW_ONLY : 0) | ((i[23] & 8) ? MH_CONV_IN_F32_STALE : 0) | ((i[23] & 16) ? MH_CONV_MASK_F32_STALE : 0), s);      // (input gradients carry no bias: p[2] = mask shadow)
-            if (i[23]) return mh_conv2d_sh2(&d, (const float*)p[0], p[5], (const float*)p[1], p[6], (const float*)p[2], (float*)p[3], (const float*)p[4], p[7], s);
+            const int fl = i[23];
+            if (fl & OPC_OUT_PLANES) return mh_conv2d_sh4(&d, (const float*)p[0], (const float*)p[1], p[6], (const float*)p[2], (float*)p[3], (const float*)p[4], p[7], p[5], s);
+            if (fl & (OPC_MASK_SHADOW | OPC_SHADOW_ONLY | OPC_IN_F32_STALE | OPC_MASK_F32_STALE))
+                return mh_conv2d_sh3(&d, (const float*)p[0], (fl & OPC_IN_SHADOW) ? p[5] : nullptr, (const float*)p[1], p[6], nullptr, (float*)p[3], (const float*)p[4],
+                                     (fl & OPC_MASK_SHADOW) ? p[2] : nullptr, p[7],
+                                     ((fl & OPC_SHADOW_ONLY) ? MH_CONV_SHADOW_ONLY : 0) | ((fl & OPC_IN_F32_STALE) ? MH_CONV_IN_F32_STALE : 0) |
+                                         ((fl & OPC_MASK_F32_STALE) ? MH_CONV_MASK_F32_STALE : 0), s);      // (input gradients carry no bias: p[2] = mask shadow)
+            if (fl) return mh_conv2d_sh2(&d, (const float*)p[0], p[5], (const float*)p[1], p[6], (const float*)p[2], (float*)p[3], (const float*)p[4], p[7], s);
             if (p[7]) return mh_conv2d_sh(&d, (const float*)p[0], (const float*)p[1], p[6], (const float*)p[2], (float*)p[3], (const float*)p[4], p[7], s);
             if (p[6]) return mh_conv2d_wb(&d, (const float*)p[0], (const float*)p[1], p[6], (const float*)p[2], (float*)p[3], (const float*)p[4], s);
             return mh_conv2d(&d, (const float*)p[0], (const float*)p[1], (const float*)p[2], (float*)p[3], (const float*)p[4], s);
@@ -358,25 +356,33 @@ struct ThreadLanes {
 };
 thread_local ThreadLanes t_lanes;
 
+int lane_device(int* dev) {
+    MH_HIP(hipGetDevice(dev));
+    MH_REQUIRE(*dev >= 0 && *dev < 16, MH_ERR_UNSUPPORTED, "device index %d out of range", *dev);
+    return 0;
+}
+// a lane set for device `dev`: one from its pool, else new streams and events
+int lanes_take(int dev, Lanes** out) {
+    LanePool& P = lane_pool();
+    Lanes* L = nullptr;
+    {
+        std::lock_guard<std::mutex> g(P.m);
+        if (!P.free_[dev].empty()) { L = P.free_[dev].back(); P.free_[dev].pop_back(); }
+    }
+    if (!L) {
+        L = new Lanes;
+        for (int k = 1; k < MH_MAX_LANES; ++k) MH_HIP(hipStreamCreateWithFlags(&L->aux[k], hipStreamNonBlocking));
+        for (auto& e : L->ev) MH_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+        L->ready = true;
+    }
+    *out = L;
+    return 0;
+}
 int lanes_get(Lanes** out) {
     int dev = 0;
-    MH_HIP(hipGetDevice(&dev));
-    MH_REQUIRE(dev >= 0 && dev < 16, MH_ERR_UNSUPPORTED, "device index %d out of range", dev);
-    if (!t_lanes.l[dev]) {
-        LanePool& P = lane_pool();
-        Lanes* L = nullptr;
-        {
-            std::lock_guard<std::mutex> g(P.m);
-            if (!P.free_[dev].empty()) { L = P.free_[dev].back(); P.free_[dev].pop_back(); }
-        }
-        if (!L) {
-            L = new Lanes;
-            for (int k = 1; k < MH_MAX_LANES; ++k) MH_HIP(hipStreamCreateWithFlags(&L->aux[k], hipStreamNonBlocking));
-            for (auto& e : L->ev) MH_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-            L->ready = true;
-        }
-        t_lanes.l[dev] = L;
-    }
+    if (int e = lane_device(&dev)) return e;
+    if (!t_lanes.l[dev])
+        if (int e = lanes_take(dev, &t_lanes.l[dev])) return e;
     *out = t_lanes.l[dev];
     return 0;
 }
@@ -512,22 +518,11 @@ struct ThreadBranches {
 thread_local ThreadBranches t_branches;
 int branch_get(int idx, Lanes** out) {
     int dev = 0;
-    MH_HIP(hipGetDevice(&dev));
-    MH_REQUIRE(dev >= 0 && dev < 16, MH_ERR_UNSUPPORTED, "device index %d out of range", dev);
+    if (int e = lane_device(&dev)) return e;
     auto& v = t_branches.sets[dev];
     while ((int)v.size() <= idx) {
-        LanePool& P = lane_pool();
         Lanes* L = nullptr;
-        {
-            std::lock_guard<std::mutex> g(P.m);
-            if (!P.free_[dev].empty()) { L = P.free_[dev].back(); P.free_[dev].pop_back(); }
-        }
-        if (!L) {
-            L = new Lanes;
-            for (int k = 1; k < MH_MAX_LANES; ++k) MH_HIP(hipStreamCreateWithFlags(&L->aux[k], hipStreamNonBlocking));
-            for (auto& e : L->ev) MH_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-            L->ready = true;
-        }
+        if (int e = lanes_take(dev, &L)) return e;
         v.push_back(L);
     }
     *out = v[idx];

@@ -301,13 +301,13 @@ def plan_table(lib, plan, stream, reps=None):
     (mh_last_kernel): which kernel family the step spends its time in, from the plan's own launch table.  The ops mutate the engine they were
     recorded on (optimizer, accumulating gradients): run it on a scratch engine.  Returns (rows, families): rows = [(index, kind, kernel, us)],
     families = {kernel template: {"launches", "us_per_step", "top_us", "top_index"}} sorted by time."""
-    from . import _ffi
+    from . import _ffi, oplayout
     rows = []
     sh = stream.cuda_stream
     reps = reps or TABLE_REPS
     for i in range(plan.n):
         one = (_ffi.Op * 1)(plan.arr[i])
-        one[0].i[26] = 0                                    # on the caller's stream, no join
+        oplayout.on_callers_stream(one[0])
         us = 1e3 * _time_ms(lib, stream, lambda: lib.plan_run(one, 1, C.c_void_p(sh)), reps)
         rows.append((i, int(plan.arr[i].kind), op_kernel_name(lib, plan.arr[i]), us))
     fam = {}
@@ -387,49 +387,45 @@ def family_report(lib, plans, stream, weights=None, nfam=12):
 def op_work(op):
     """(algorithmic flops, algorithmic bytes) of a conv / filter-gradient op record (SURVEY 8(d) definitions), else (0, 0)"""
     from . import _ffi
+    from .oplayout import LAYOUT, fields
+    if op.kind not in LAYOUT:
+        return 0.0, 0.0
+    o = fields(op)
     if op.kind in (_ffi.OP_CONV_PLANES, _ffi.OP_CONV_PLANES_BWD):
         # planes layers: operands and results are bf16 planes: in 2 (hi, lo) x 2 B forward / 1 x 2 B backward per element, out likewise (+ 4 B where the
-        # fp32 copy is stored)
-        i = op.i
-        B, H, W, K, N = i[0], i[1], i[2], i[5], i[6]
+        # fp32 copy is stored).  (B, Hi, Wi: the forward layer's input -- stride 1, so also its output)
+        B, H, W, K, N = o.B, o.Hi, o.Wi, o.K, o.N
         fwd = op.kind == _ffi.OP_CONV_PLANES
         cin, cout = (K, N) if fwd else (N, K)
         pl = 2 if fwd else 1
-        f32 = 4.0 if op.p[4 if fwd else 3] else 0.0
-        mask = 2.0 * cout if (not fwd and op.p[2]) else 0.0      # the input gradient reads the activation's hi plane once for the sign test
+        f32 = 4.0 if (o.out if fwd else o.dx) else 0.0
+        mask = 2.0 * cout if (not fwd and o.mask_hi) else 0.0      # the input gradient reads the activation's hi plane once for the sign test
         return 2.0 * B * H * W * 9 * K * N, B * H * W * (cin * 2.0 * pl + cout * (2.0 * pl + f32) + mask) + 9 * K * N * 2.0 * pl
     # correlation family: HBM-bound, bytes = every operand once (SURVEY 8(d): forward B H W (2C + D) 4, gradient B H W (4C + D) 4; the fused forms add what they fuse)
-    if op.kind == _ffi.OP_CORR_FWD:
-        B, H, W, Cc, md, st = op.i[4], op.i[5], op.i[6], op.i[7], op.i[8], op.i[9]
-        D = 2 * md // max(st, 1) + 1
-        return 2.0 * B * H * W * Cc * D, 4.0 * B * H * W * (2 * Cc + D + (Cc if op.i[10] else 0))
-    if op.kind == _ffi.OP_CORR_BWD:
-        B, H, W, Cc, md, st = op.i[9], op.i[10], op.i[11], op.i[12], op.i[13], op.i[14]
-        D = 2 * md // max(st, 1) + 1
-        return 4.0 * B * H * W * Cc * D, 4.0 * B * H * W * (4 * Cc + D + (Cc if op.i[15] else 0))
-    if op.kind == _ffi.OP_CORR_WARP_BWD:
-        B, H, W, Cc, md, st = op.i[8], op.i[9], op.i[10], op.i[11], op.i[12], op.i[13]
-        D = 2 * md // max(st, 1) + 1
-        return 4.0 * B * H * W * Cc * D, 4.0 * B * H * W * (8 * Cc + D + 3)        # reads g (C + D + 1), L, Rw, the right features, u, dL, dimg; writes dL, dimg, du
+    if op.kind in (_ffi.OP_CORR_FWD, _ffi.OP_CORR_BWD, _ffi.OP_CORR_WARP_BWD):
+        D = 2 * o.md // max(o.stride, 1) + 1
+        pix = o.B * o.H * o.W
+        if op.kind == _ffi.OP_CORR_FWD:
+            return 2.0 * pix * o.Cc * D, 4.0 * pix * (2 * o.Cc + D + (o.Cc if o.copy_left else 0))
+        if op.kind == _ffi.OP_CORR_BWD:
+            return 4.0 * pix * o.Cc * D, 4.0 * pix * (4 * o.Cc + D + (o.Cc if o.copy_left else 0))
+        return 4.0 * pix * o.Cc * D, 4.0 * pix * (8 * o.Cc + D + 3)        # reads g (C + D + 1), L, Rw, the right features, u, dL, dimg; writes dL, dimg, du
     if op.kind == _ffi.OP_CONV_IMAGE:
-        NB, H0, W0, Cc, Hp, Wp, N, st = op.i[0], op.i[1], op.i[2], op.i[3], op.i[4], op.i[5], op.i[8], op.i[9]
-        Ho, Wo = (Hp + st - 1) // st, (Wp + st - 1) // st
-        return 2.0 * NB * Ho * Wo * 9 * Cc * N, 4.0 * (NB * H0 * W0 * Cc + NB * Ho * Wo * N + 9 * Cc * N) + (2.0 * NB * Ho * Wo * N if op.p[4] else 0.0)
+        NB, Cc, N, st = o.NB, o.Cc, o.N, o.stride
+        Ho, Wo = (o.Hp + st - 1) // st, (o.Wp + st - 1) // st
+        return 2.0 * NB * Ho * Wo * 9 * Cc * N, 4.0 * (NB * o.H0 * o.W0 * Cc + NB * Ho * Wo * N + 9 * Cc * N) + (2.0 * NB * Ho * Wo * N if o.shadow else 0.0)
     if op.kind == _ffi.OP_LEVEL_FRONT:
-        B, H, W, Cc, md = op.i[7], op.i[8], op.i[9], op.i[10], op.i[11]
-        D = 2 * md + 1
+        B, H, W, Cc = o.B, o.H, o.W, o.Cc
+        D = 2 * o.md + 1
         fl, by = 2.0 * B * H * W * Cc * D, 4.0 * B * H * W * (2 * Cc + (Cc + D + 1) + Cc + 1)        # reads L, R; writes [L | corr | u], the warped features, u
-        if op.p[8]:                 # + the coarser level's disparity head (3x3, K -> 1): reads its input once, writes the coarse disparity
-            Hc, Wc, K = op.i[0], op.i[1], op.i[15]
-            fl += 2.0 * B * Hc * Wc * 9 * K
-            by += 4.0 * B * Hc * Wc * (K + 1)
+        if o.X:                     # + the coarser level's disparity head (3x3, K -> 1): reads its input once, writes the coarse disparity
+            fl += 2.0 * B * o.Hc * o.Wc * 9 * o.K
+            by += 4.0 * B * o.Hc * o.Wc * (o.K + 1)
         return fl, by
     if op.kind not in (_ffi.OP_CONV, _ffi.OP_WGRAD, _ffi.OP_WGRAD_PARTIAL):
         return 0.0, 0.0
-    i = op.i
-    B, Hi, Wi, Ho, Wo, K, N, kh, kw, mode = i[0], i[1], i[2], i[3], i[4], i[5], i[6], i[7], i[8], i[13]
-    pix = Ho * Wo if (mode == 0 or op.kind != _ffi.OP_CONV) else Hi * Wi
-    return 2.0 * B * pix * kh * kw * K * N, 4.0 * (B * Hi * Wi * K + B * Ho * Wo * N + kh * kw * K * N)
+    pix = o.Ho * o.Wo if (o.mode == 0 or op.kind != _ffi.OP_CONV) else o.Hi * o.Wi
+    return 2.0 * o.B * pix * o.kh * o.kw * o.K * o.N, 4.0 * (o.B * o.Hi * o.Wi * o.K + o.B * o.Ho * o.Wo * o.N + o.kh * o.kw * o.K * o.N)
 
 
 def tail_stamps(lib, E, mk, feed, args, dev, plain_ms):

@@ -2,8 +2,17 @@
 stored at all.  A mixin of MadNetEngine: the passes read the engine's tensor lists (E, Cx, dE, dCx), its library handle and its Schedule."""
 import ctypes as C
 
-from . import _ffi
+from . import _ffi, oplayout
 from .netdef import LEVELS
+from .oplayout import fields
+
+
+def _dgrad(op, bit):
+    """fields of `op` if it is an input gradient of the tiled families in the bf16 arithmetic that was given the shadow `bit` names, else None"""
+    if op.kind != _ffi.OP_CONV:
+        return None
+    f = fields(op)
+    return f if (f.mode == 1 and f.precision == 1 and (f.flags & bit)) else None
 
 
 class ElisionPasses(object):
@@ -18,28 +27,23 @@ class ElisionPasses(object):
         n = 0
         spans = []
         for idx, o in enumerate(ops_):
-            if o.kind == _ffi.OP_CONV and o.i[13] == 1 and o.p[7] and not o.i[18] and o.i[22] == 1 and o.p[3]:
-                spans.append((idx, int(o.p[3]), int(o.p[3]) + 4 * o.i[0] * o.i[3] * o.i[4] * o.i[16]))
+            f = fields(o) if o.kind == _ffi.OP_CONV else None
+            if f and f.mode == 1 and f.shadow and not f.accumulate and f.precision == 1 and f.out:
+                spans.append((idx, int(f.out), int(f.out) + 4 * f.B * f.Ho * f.Wo * f.out_ld))
         for idx, lo, hi in spans:
-            if any(a < hi and lo < a + nb for _, a, nb in getattr(r, "refs", ())):
+            if any(a < hi and lo < a + nb for _, a, nb in r.refs):
                 continue                # a device table (cast / split segment) reads the map
-            users = []
-            for j, q in enumerate(ops_):
-                if j == idx:
-                    continue
-                if any(q.p[k] and lo <= int(q.p[k]) < hi for k in range(len(q.p))):
-                    users.append(j)
+            users = [j for j, q in enumerate(ops_) if j != idx and oplayout.pointers_into(q, lo, hi)]
             if len(users) != 1 or users[0] < idx:
                 continue
             c = ops_[users[0]]
-            if not (c.kind == _ffi.OP_CONV and c.i[13] == 1 and int(c.p[0]) == lo and (c.i[23] & 1) and c.i[22] == 1):
-                continue
-            if sum(1 for k in range(len(c.p)) if c.p[k] and lo <= int(c.p[k]) < hi) != 1:
+            cf = _dgrad(c, oplayout.CONV_IN_SHADOW)
+            if not (cf and int(cf.inp) == lo and len(oplayout.pointers_into(c, lo, hi)) == 1):
                 continue
             if not (self._takes_shadows(c) & 1):
                 continue
-            ops_[idx].i[23] |= 4
-            c.i[23] |= 8            # MH_CONV_IN_F32_STALE: a replay whose dispatch no longer stages the shadow is refused, not wrong
+            fields(ops_[idx]).flags |= oplayout.CONV_SHADOW_ONLY
+            cf.flags |= oplayout.CONV_IN_F32_STALE          # a replay whose dispatch no longer stages the shadow is refused, not wrong
             self._note_elided(r, lo, hi - lo)
             n += 1
         return n
@@ -48,8 +52,6 @@ class ElisionPasses(object):
         """An fp32 buffer no op of this plan writes any more.  Kept on the recorder / plan (plan.elided) so that a reader OUTSIDE the plan can ask; with
         MH_POISON_ELIDED=1 (tests) the buffer is filled with NaN at once: an op that still reads it -- a device-table op whose table building forgot
         Recorder.note_refs, a debug read of engine.E / Cx -- then fails loudly instead of consuming a stale map."""
-        if not hasattr(r, "elided"):
-            r.elided = []
         r.elided.append((int(ptr), int(nbytes)))
         if self.sched.POISON_ELIDED:
             t = self._tensor_by_ptr().get(int(ptr))
@@ -67,8 +69,8 @@ class ElisionPasses(object):
 
     def _takes_shadows(self, c):
         """mh_conv2d_takes_shadows for a recorded OP_CONV: bit 1 = the launch stages in_shadow, bit 2 = it reads the mask from mask_shadow"""
-        d = _ffi.ConvDesc(*([c.i[k] for k in range(18)] + [c.i[18], c.f[0], c.f[1], c.i[19], c.i[20], c.i[22]]))
-        return self.lib.conv2d_takes_shadows(C.byref(d), C.c_void_p(c.p[0]), C.c_void_p(c.p[1]), C.c_void_p(c.p[6]), C.c_void_p(c.p[3]), C.c_void_p(c.p[4]))
+        d, f = oplayout.conv_desc(c), fields(c)
+        return self.lib.conv2d_takes_shadows(C.byref(d), C.c_void_p(f.inp), C.c_void_p(f.w), C.c_void_p(f.wb), C.c_void_p(f.out), C.c_void_p(f.mask))
 
     def _standalone_activations(self):
         """{data pointer: bytes} of the activation tensors that are allocations of their own (no view of them can start in front of them): the only
@@ -98,42 +100,45 @@ class ElisionPasses(object):
         cand = self._standalone_activations()
         n = 0
         for idx, o in enumerate(ops_):
-            if o.kind == _ffi.OP_CONV_PLANES and o.p[4] and o.p[5] and o.p[6]:
-                slot = 4                    # forward: fp32 result beside both planes
-            elif o.kind == _ffi.OP_CONV_PLANES_BWD and o.p[3] and o.p[4]:
-                slot = 3                    # input gradient: fp32 map beside its shadow
+            if o.kind not in (_ffi.OP_CONV_PLANES, _ffi.OP_CONV_PLANES_BWD):
+                continue
+            f = fields(o)
+            if o.kind == _ffi.OP_CONV_PLANES and f.out and f.out_hi and f.out_lo:
+                slot = "out"                # forward: fp32 result beside both planes
+            elif o.kind == _ffi.OP_CONV_PLANES_BWD and f.dx and f.dx_hi:
+                slot = "dx"                 # input gradient: fp32 map beside its shadow
             else:
                 continue
-            lo = int(o.p[slot])
+            lo = int(getattr(f, slot))
             if lo not in cand:
                 continue
             hi = lo + cand[lo]
-            if any(a < hi and lo < a + nb for _, a, nb in getattr(r, "refs", ())):
+            if any(a < hi and lo < a + nb for _, a, nb in r.refs):
                 continue
             ok, mask_users = True, []
             for j, q in enumerate(ops_):
                 if j == idx:
                     continue
-                hits = [k for k in range(len(q.p)) if q.p[k] and lo <= int(q.p[k]) < hi]
+                hits = oplayout.pointers_into(q, lo, hi)
                 if not hits:
                     continue
                 # the only tolerated readers: an input gradient (tiled families) that was given this tensor as its leaky mask TOGETHER with the mask's
                 # shadow and whose kernel tests the shadow -- or as its dz together with dz's shadow and whose kernel stages the shadow
-                if (q.kind == _ffi.OP_CONV and q.i[13] == 1 and hits == [4] and int(q.p[4]) == lo and (q.i[23] & 2) and q.i[22] == 1
-                        and (self._takes_shadows(q) & 2)):
-                    mask_users.append((q, 16))          # MH_CONV_MASK_F32_STALE
+                qf = _dgrad(q, oplayout.CONV_MASK_SHADOW)
+                if qf and hits == ["mask"] and int(qf.mask) == lo and (self._takes_shadows(q) & 2):
+                    mask_users.append((qf, oplayout.CONV_MASK_F32_STALE))
                     continue
-                if (q.kind == _ffi.OP_CONV and q.i[13] == 1 and hits == [0] and int(q.p[0]) == lo and (q.i[23] & 1) and q.i[22] == 1
-                        and (self._takes_shadows(q) & 1)):
-                    mask_users.append((q, 8))           # MH_CONV_IN_F32_STALE
+                qf = _dgrad(q, oplayout.CONV_IN_SHADOW)
+                if qf and hits == ["inp"] and int(qf.inp) == lo and (self._takes_shadows(q) & 1):
+                    mask_users.append((qf, oplayout.CONV_IN_F32_STALE))
                     continue
                 ok = False
                 break
             if not ok:
                 continue
-            o.p[slot] = None
-            for q, bit in mask_users:
-                q.i[23] |= bit
+            setattr(f, slot, None)
+            for qf, bit in mask_users:
+                qf.flags |= bit
             self._note_elided(r, lo, hi - lo)
             n += 1
         return n

@@ -17,7 +17,7 @@ import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 PKG = os.path.join(ROOT, "real-time-self-adaptive-deep-stereo_amd")
 sys.path[:0] = [ROOT, PKG]
-from madnet_hip import _ffi, ops, engine as E, dispnet_engine as DE      # noqa: E402
+from madnet_hip import _ffi, ops, oplayout, engine as E, dispnet_engine as DE      # noqa: E402
 
 # (tag, B, H, W, Cin, Cout of the forward layer, hook name, hook value, value that restores the default, fragment bank)
 FAMILIES = [
@@ -130,10 +130,10 @@ def queried(lib, dev):
                         c = plan.arr[k]
                         if c.kind != _ffi.OP_CONV:
                             continue
-                        ints = [c.i[j] for j in range(18)] + [c.i[18], c.f[0], c.f[1], c.i[19], c.i[20], c.i[22]]         # (as elision._takes_shadows)
-                        d = _ffi.ConvDesc(*ints)
-                        bits = q(C.byref(d), C.c_void_p(c.p[0]), C.c_void_p(c.p[1]), C.c_void_p(c.p[6]), C.c_void_p(c.p[3]), C.c_void_p(c.p[4]))
-                        print("b", "%dx%d B=%d %s %s op %d" % (H, W, B, net, prec, k), " ".join(str(v) for v in ints), "bank=%d mask=%d" % (bool(c.p[6]), bool(c.p[4])),
+                        d, f = oplayout.conv_desc(c), oplayout.fields(c)
+                        ints = [getattr(d, name) for name, _ in d._fields_]
+                        bits = q(C.byref(d), C.c_void_p(f.inp), C.c_void_p(f.w), C.c_void_p(f.wb), C.c_void_p(f.out), C.c_void_p(f.mask))
+                        print("b", "%dx%d B=%d %s %s op %d" % (H, W, B, net, prec, k), " ".join(str(v) for v in ints), "bank=%d mask=%d" % (bool(f.wb), bool(f.mask)),
                               "takes=%d" % bits)
                     eng.close()
                     sys.stdout.flush()

@@ -5,7 +5,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 for p in (ROOT, os.path.join(ROOT, "real-time-self-adaptive-deep-stereo_amd")):
     sys.path.insert(0, p)
 import torch
-from madnet_hip import _ffi, engine as E, dispnet_engine as DE, synthetic as S, benchtools as BT
+from madnet_hip import _ffi, engine as E, dispnet_engine as DE, synthetic as S, benchtools as BT, oplayout
 
 ap = argparse.ArgumentParser()
 ap.add_argument("--model", default="madnet"); ap.add_argument("--precision", default="mixed"); ap.add_argument("--mode", default="FULL")
@@ -33,4 +33,4 @@ for k, v in fam.items():
 print()
 for i, kind, k, us in rows[:a.rows]:
     fl, by = plan.work.get(i, BT.op_work(plan.arr[i]))
-    print("%4d kind %2d lane %d %8.1f us  %7.1f TF/s  %s" % (i, kind, plan.arr[i].i[26] & 0xff, us, fl / us * 1e-6 if us > 0 else 0, k[:110]))
+    print("%4d kind %2d lane %d %8.1f us  %7.1f TF/s  %s" % (i, kind, oplayout.lane_of(plan.arr[i]), us, fl / us * 1e-6 if us > 0 else 0, k[:110]))

@@ -16,7 +16,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 for p in (ROOT, os.path.join(ROOT, "real-time-self-adaptive-deep-stereo_amd")):
     sys.path.insert(0, p)
 import torch
-from madnet_hip import _ffi, engine as E, dispnet_engine as DE, synthetic as S, benchtools as BT, ops
+from madnet_hip import _ffi, engine as E, dispnet_engine as DE, synthetic as S, benchtools as BT, ops, oplayout
 
 lib = _ffi.lib()
 for item in filter(None, os.environ.get("PMC_TUNE", "").split(",")):          # PMC_TUNE="conv_bank_small=0": library tuning hooks applied before anything is recorded
@@ -40,7 +40,7 @@ def run_plan_ops(plan, tag, only_new=False):
         if plan.arr[i].kind not in KINDS:
             continue
         one = (_ffi.Op * 1)(plan.arr[i])
-        one[0].i[26] = 0
+        oplayout.on_callers_stream(one[0])
         separator()
         lib.plan_run(one, 1, None)
         kname = BT.op_kernel_name(lib, plan.arr[i])

@@ -57,3 +57,19 @@ def test_struct_layout_matches_header():
     assert ctypes.sizeof(_ffi.Op) == 4 + 27 * 4 + 4 * 4 + 12 * 8 + 8
     assert ctypes.sizeof(_ffi.ShadowSeg) == 2 * 8 + 8 + 4 * 4 and ctypes.sizeof(_ffi.WgsLayer) == 4 * 8 + 14 * 4
     assert ctypes.sizeof(_ffi.PlaneSeg) == 3 * 8 + 8 + 4 * 4 + 8 + 2 * 4
+
+
+def test_op_kinds_and_limits_match_the_python_mirrors():
+    """the MH_OP_* enum (numbered from 1, comments stripped) and the plan executor's limits of the header against _ffi, name for name, value for value"""
+    from madnet_hip import _ffi
+    src = re.sub(r"/\*.*?\*/", "", open(HEADER).read(), flags=re.S)
+    body = re.search(r"enum\s*\{\s*(MH_OP_CONV\s*=\s*1\b.*?)\}", src, flags=re.S).group(1)
+    names = [t.split("=")[0].strip() for t in body.split(",") if t.strip()]
+    assert all(re.match(r"MH_OP_[A-Z0-9_]+$", n) for n in names) and "=" not in body.replace("MH_OP_CONV = 1", "", 1)
+    header = {n[3:]: k for k, n in enumerate(names, 1)}
+    mirror = {n: v for n, v in vars(_ffi).items() if n.startswith("OP_") and n not in ("OP_JOIN", "OP_NODEFER")}
+    assert len(header) == 41 and header == mirror
+    defines = dict((n, int(v, 0)) for n, v in re.findall(r"#define\s+(MH_[A-Z_]+)\s+(0x[0-9a-fA-F]+|\d+)\b", src))
+    for c_name, py_name in (("MH_MAX_LANES", "MAX_LANES"), ("MH_OP_JOIN", "OP_JOIN"), ("MH_OP_NODEFER", "OP_NODEFER"), ("MH_FETCH_MAX", "FETCH_MAX"),
+                            ("MH_ALLREDUCE_MAX_BUFS", "ALLREDUCE_MAX_BUFS")):
+        assert defines[c_name] == getattr(_ffi, py_name), c_name

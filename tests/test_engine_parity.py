@@ -8,6 +8,7 @@ import pytest
 import torch
 
 from madnet_hip import engine as E
+from madnet_hip.oplayout import fields
 from madnet_hip import synthetic as S
 from oracle import madnet as OM
 
@@ -693,7 +694,8 @@ def test_step_with_streamed_filter_gradients_emulated(mode):
     for name, _shape in P.manifest:        # (the bias gradients meet in fp32 atomics whose order is free)
         a, b = engc.params.tensor(name, "g"), e1.params.tensor(name, "g")
         assert torch.equal(a, b) if name.endswith("/weights") else (a - b).abs().max().item() <= 1e-6 * max(a.abs().max().item(), 1e-6), name
-    assert sum(o.i[0] for o in planc.arr if o.kind == _ffi.OP_SHADOW_CAST) > sum(o.i[0] for o in res[True][4].last_plan_arr if o.kind == _ffi.OP_SHADOW_CAST)
+    nseg = lambda arr: sum(fields(o).nseg for o in arr if o.kind == _ffi.OP_SHADOW_CAST)
+    assert nseg(planc.arr) > nseg(res[True][4].last_plan_arr)
 
 
 def test_step_with_fused_head_backward_emulated():
@@ -870,10 +872,11 @@ def test_step_with_bf16_only_gradient_maps(bname, size):
             eng.set_inputs(l, r, gt[..., 0])
             plan = eng.build_plan("FULL", lr=1e-4, update=False)
             # (input gradients on mh_conv2d_planes_bwd, round 4: p = dz_hi, bank, mask_hi, dx, dx_hi -- fp32 elided = no dx, mask = a shadow's sign)
-            from madnet_hip import _ffi
-            pb = [plan.arr[k] for k in range(plan.n) if plan.arr[k].kind == _ffi.OP_CONV_PLANES_BWD]
-            n_only = sum(1 for k in range(plan.n) if plan.arr[k].kind == 1 and plan.arr[k].i[23] & 4) + sum(1 for o in pb if not o.p[3])
-            n_mask = sum(1 for k in range(plan.n) if plan.arr[k].kind == 1 and plan.arr[k].i[23] & 2) + sum(1 for o in pb if o.p[2])
+            from madnet_hip import _ffi, oplayout
+            pb = [fields(o) for o in plan.arr if o.kind == _ffi.OP_CONV_PLANES_BWD]
+            cv = [fields(o) for o in plan.arr if o.kind == _ffi.OP_CONV]
+            n_only = sum(1 for f in cv if f.flags & oplayout.CONV_SHADOW_ONLY) + sum(1 for f in pb if not f.dx)
+            n_mask = sum(1 for f in cv if f.flags & oplayout.CONV_MASK_SHADOW) + sum(1 for f in pb if f.mask_hi)
             for k in E.LEVELS:
                 for t in eng.dE[k]:
                     t.fill_(float("nan"))
@@ -1064,10 +1067,10 @@ def test_mixed_forward_from_planes_matches_fp32_operand_path(bname, mode):
             nplanes = lib.tune_conv_planes(0)
             pops = [plan.arr[i] for i in range(plan.n)]
             kinds = [o.kind for o in pops]
-            elided = sum(1 for o in pops if o.kind == _ffi.OP_CONV_PLANES and not o.p[4])
+            elided = sum(1 for o in pops if o.kind == _ffi.OP_CONV_PLANES and not fields(o).out)
             res[planes] = dict(pred=eng.pred.cpu().clone(), loss=eng.res_loss[0].item(), w={n: eng.params.tensor(n).cpu().clone() for n in wn},
                                nplanes=nplanes, nrec=kinds.count(_ffi.OP_CONV_PLANES), elided=elided, splits=kinds.count(_ffi.OP_PLANE_SPLIT),
-                               nbwd=kinds.count(_ffi.OP_CONV_PLANES_BWD), bwd_elided=sum(1 for o in pops if o.kind == _ffi.OP_CONV_PLANES_BWD and not o.p[3]))
+                               nbwd=kinds.count(_ffi.OP_CONV_PLANES_BWD), bwd_elided=sum(1 for o in pops if o.kind == _ffi.OP_CONV_PLANES_BWD and not fields(o).dx))
     finally:
         lib.tune_conv_bank(-1); lib.tune_conv_patch(-1)
     a, b = res[True], res[False]

@@ -7,6 +7,7 @@ import pytest
 import torch
 
 from madnet_hip import _ffi, ops
+from madnet_hip.oplayout import fields, sched_word
 
 ERR_ARG, ERR_ALIGN, ERR_UNSUPPORTED = -1, -2, -3
 
@@ -92,7 +93,7 @@ def test_corr_and_misc_argument_checks(backend):
     # plan executor: unknown op kind / lane out of range, reported with the op index
     op = (_ffi.Op * 1)(); op[0].kind = 99
     assert _raw(backend, "plan_run")(op, 1, None) == ERR_ARG and "plan op 0" in _msg(backend)
-    op[0].kind = _ffi.OP_FILL; op[0].i[26] = 7
+    op[0].kind = _ffi.OP_FILL; fields(op[0]).sched = sched_word(7)
     assert _raw(backend, "plan_run")(op, 1, None) == ERR_ARG and "lane" in _msg(backend)
 
 
@@ -142,7 +143,7 @@ def test_round3_entry_points_argument_checks(backend):
     finally:
         backend.lib.tune_conv_patch(-1)
     # mh_plans_run: a plan that uses the last lane (reserved for the branch streams) is refused
-    op = (_ffi.Op * 1)(); op[0].kind = _ffi.OP_FILL; op[0].i[26] = 4
+    op = (_ffi.Op * 1)(); op[0].kind = _ffi.OP_FILL; fields(op[0]).sched = sched_word(_ffi.MAX_LANES - 1)
     refs = (_ffi.PlanRef * 1)(); refs[0].ops, refs[0].nops = C.addressof(op), 1
     assert _raw(backend, "plans_run")(refs, 1, None) < 0 and "lane" in _msg(backend)
     assert _raw(backend, "plans_run")(refs, 0, None) == ERR_ARG

@@ -12,6 +12,7 @@ from madnet_hip import _ffi
 from madnet_hip import dispnet_engine as DE
 from madnet_hip import engine as E
 from madnet_hip import ops
+from madnet_hip.oplayout import lane_of
 from madnet_hip import synthetic as S
 from oracle import dispnet as OD
 from oracle import madnet as OM
@@ -109,7 +110,7 @@ def test_default_plans_are_unchanged_and_the_report_is_one_more_op(backend, net)
         assert _ffi.OP_METRICS_KITTI not in [f[0] for f in off]
         assert kinds.count(_ffi.OP_METRICS_KITTI) == 1
         at = kinds.index(_ffi.OP_METRICS_KITTI)
-        assert kinds[at - 1] == _ffi.OP_METRICS and (plan.arr[at].i[26] & 0xff) == (plan.arr[at - 1].i[26] & 0xff)
+        assert kinds[at - 1] == _ffi.OP_METRICS and lane_of(plan.arr[at]) == lane_of(plan.arr[at - 1])
         assert on[:at] + on[at + 1:] == off
 
 

@@ -5,6 +5,7 @@ import pytest
 import torch
 
 from madnet_hip import ops, engine as E, synthetic as S
+from madnet_hip.oplayout import fields, lane_of
 from oracle import madnet as OM
 from test_conv_parity import _rand, _padded, _oracle_grads, _bf
 from test_engine_parity import _backend, _ffi_mod
@@ -104,7 +105,7 @@ def _image_layer_kernel_ab(backend, H, W):
             eng = E.MadNetEngine(backend.lib, H, W, B=1, device=backend.device, weights=wn, precision="mixed")
             eng.set_inputs(l, r, gt[..., 0])
             plan = eng.build_plan("FULL", lr=1e-4, update=False)
-            splits = [o.i[23] for o in plan.arr if o.kind == F.OP_WGRAD_PARTIAL and o.i[5] == 3]
+            splits = [fields(o).splits for o in plan.arr if o.kind == F.OP_WGRAD_PARTIAL and fields(o).K == 3]
             plan.run(backend.lib, 0)
             backend.sync()
         finally:
@@ -143,9 +144,9 @@ def _early_update_ab(backend, H, W, precision):
             plan = eng.build_plan("FULL", lr=1e-3)
             P = eng.params
             mom = [o for o in plan.arr if o.kind == F.OP_MOMENTUM]
-            spans = sorted(((o.p[0] - P.w.data_ptr()) // 4, (o.p[0] - P.w.data_ptr()) // 4 + o.n) for o in mom)
+            spans = sorted(((fields(o).var - P.w.data_ptr()) // 4, (fields(o).var - P.w.data_ptr()) // 4 + o.n) for o in mom)
             assert spans[0][0] == 0 and spans[-1][1] == P.total and all(a[1] == b[0] for a, b in zip(spans, spans[1:])), spans       # a partition
-            on_side = sum(1 for o in mom if (o.i[26] & 0xff) > 0)
+            on_side = sum(1 for o in mom if lane_of(o) > 0)
             assert (len(mom) >= 6 and on_side >= len(mom) - 1) if early else (len(mom) == 1 and on_side == 0), (len(mom), on_side)
             snaps = []
             for _ in range(2):
