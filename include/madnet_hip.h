@@ -380,6 +380,32 @@ int mh_fetch_inputs(const mh_input_table* table, float* const* dst, const int64_
 /* device-side address of a page-locked (hipHostMalloc / torch pin_memory) host allocation */
 int mh_host_device_pointer(void* host, void** device);
 
+/* ---- Train.py's input side on the device: the reference crops, augments and casts every training sample inside tf.data (preprocessing.random_crop and
+ *      preprocessing.augment, Data_utils/preprocessing.py:31-89, mapped over the set in Data_utils/data_reader.py:140-153; centre crop / zero pad of
+ *      resize_image_with_crop_or_pad, :150, outside training).  Here the host uploads the decoded 8-bit frames as they are and one call cuts sample b's H x W
+ *      window at (r0, c0) out of its own Hs x Ws source -- outside the source the window reads 0 -- and applies, in this order: cast; + delta (active bit 0);
+ *      (x - m) * contrast + m with m = the per-channel mean over the window of that view after the brightness step (bit 1); RGB -> HSV, h = (h + hue) mod 1,
+ *      HSV -> RGB (bit 2); clip to [0, 255].  Both views of a sample take the same parameters; the ground truth is only cut (gt_kind 1: uint16 / 256, the KITTI
+ *      PNG).  left, right: [B,H,W,3], gt: [B,H,W,1] float32, dense, every element written.  Per pixel the fp32 operations and their order are those of the host
+ *      statement (Data_utils/data_reader.augment of this package), un-contracted: without bit 1 the result equals it bit for bit.  The mean is a two-stage
+ *      fixed-order sum in float64 (no atomics: two calls give the same bits): a first launch writes per-workgroup partial sums to `ws` (8-byte aligned,
+ *      mh_frame_prepare_ws_floats floats), the applying launch finishes them.  ws == NULL: the caller states that no sample has bit 1 set -- one launch; a
+ *      sample that has it set nonetheless gets NaN images.  `segs` must be readable by the device when the kernels run: device memory, or page-locked host
+ *      memory through mh_host_device_pointer.  H * W * 3 < 2^31, 2 * B < 65536. */
+typedef struct mh_frame_seg {
+    const void* left; const void* right;   /* uint8 [Hs][Ws][3], this sample's whole decoded frames          */
+    const void* gt;                         /* [Hs][Ws]: float32, or uint16 (value / 256, KITTI) by gt_kind   */
+    int32_t Hs, Ws;                         /* source size: differs from sample to sample                     */
+    int32_t r0, c0;                         /* window origin in the source; may be negative / run past the    */
+                                            /* edge: outside the source the window reads 0 (centre pad)       */
+    int32_t gt_kind;                        /* 0 float32, 1 uint16/256                                        */
+    int32_t active;                         /* bit 0 brightness, bit 1 contrast, bit 2 hue                    */
+    float delta, contrast, hue;
+} mh_frame_seg;
+int64_t mh_frame_prepare_ws_floats(int32_t B, int32_t H, int32_t W);
+int mh_frame_prepare(const mh_frame_seg* segs, int32_t B, int32_t H, int32_t W,
+                     float* left, float* right, float* gt, float* ws, void* stream);
+
 /* ---- preprocessing.pad_image (REFLECT, preprocessing.py:7-29) fused with the float cast
  *      and the channel padding 3 -> out_ld (extra channels zero) ------------------------ */
 /* out = in / div - sub  (MADNet: div=1, sub=0; DispNet._preprocess_inputs, DispNet.py:59-73: x/255 - 100/255) */

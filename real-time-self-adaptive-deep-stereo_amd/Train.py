@@ -8,7 +8,10 @@ decayed rate and then hands args.lr to AdamOptimizer).  Not carried over: Tensor
 dumps (Train.py:86-87,105-107,112) -- the loss / EPE / bad3 go to <output>/train_log.csv instead; --validationSet is
 evaluated with the current weights every 1000 steps on one batch (the reference only wires it into the summaries).
 Multi-GPU: launch with `python -m torch.distributed.run --nproc-per-node N Train.py ...`: one process per GPU, each on its own
-shard of the shuffled stream, gradients all-reduced over RCCL every step."""
+shard of the shuffled stream, gradients all-reduced over RCCL every step.
+Input: --prepareOn host (default) crops, augments and casts every sample in the Python reader thread and uploads float32 batches;
+--prepareOn device uploads the decoded 8-bit frames and does the three on the GPU (mh_frame_prepare on the prefetcher's copy stream) --
+the same samples, windows and parameters for the same seed; --inputWorkers N decodes on N threads."""
 import argparse
 import datetime
 import os
@@ -58,11 +61,12 @@ def main(args):
                          % (n_pred, args.modelName, len(args.lossWeights)))
     data_set = data_reader.dataset(args.trainingSet, batch_size=args.batchSize, crop_shape=args.imageShape,
                                    num_epochs=args.numEpochs, augment=args.augment, is_training=True, shuffle=True, seed=rank,
-                                   shard=(rank, world))
+                                   shard=(rank, world), prepare=args.prepareOn, workers=args.inputWorkers)
     validation_set = None
     if args.validationSet is not None:
         validation_set = data_reader.dataset(args.validationSet, batch_size=args.batchSize, crop_shape=args.imageShape,
-                                             augment=False, is_training=False, shuffle=True, seed=1000 + rank, num_epochs=10 ** 6)
+                                             augment=False, is_training=False, shuffle=True, seed=1000 + rank, num_epochs=10 ** 6,
+                                             prepare=args.prepareOn, workers=args.inputWorkers)
     B = args.batchSize
     net_args = {'left_img': torch.zeros(B, H, W, 3, device=dev), 'right_img': torch.zeros(B, H, W, 3, device=dev),
                 'split_layers': [None], 'sequence': True, 'train_portion': 'BEGIN', 'bulkhead': False,
@@ -91,7 +95,8 @@ def main(args):
                     step_eval, out['loss'], fbTime, datetime.timedelta(seconds=missing_time)))
                 val = ('', '')
                 if val_iter is not None and step_eval % 1000 == 0:
-                    vl, vr, vg = next(val_iter)
+                    vb = next(val_iter)
+                    vl, vr, vg = data_reader.prepare_on_device(vb, dev) if isinstance(vb, data_reader.raw_batch) else vb
                     val = validate(stereo_net, vl, vr, vg)
                 log.write('%d,%.6f,%.4f,%.5f,%s,%s\n' % (step_eval, out['loss'], out['epe'], out['bad3'], val[0], val[1]))
                 log.flush()
@@ -112,7 +117,7 @@ def validate(stereo_net, left, right, gt):
     eng = stereo_net.engine
     if not hasattr(eng, '_val_plan'):
         eng._val_plan = eng.build_plan('NONE')
-    eng.set_inputs(left, right, np.asarray(gt)[..., 0])
+    eng.set_inputs(left, right, gt[..., 0])
     eng._val_plan.run(stereo_net._lib, 0)
     torch.cuda.synchronize()
     m = eng.res_met.cpu().numpy()
@@ -131,6 +136,8 @@ def build_parser():
     parser.add_argument("--batchSize", help='samples per step (per GPU)', type=int, default=4)
     parser.add_argument("--numEpochs", help='passes over the training list', type=int, default=50)
     parser.add_argument("--augment", help="colour augmentation of the two views", action='store_true')
+    parser.add_argument("--prepareOn", help="where crop, augmentation and float cast run: host (Python reader thread) or device (HIP kernels behind the upload of the decoded 8-bit frames)", choices=['host', 'device'], default='host')
+    parser.add_argument("--inputWorkers", help="threads that decode the images ahead of the step", type=int, default=1)
     parser.add_argument("--lossWeights", help="weight of the loss at each predicted scale, full resolution first", nargs='+', default=None, type=float)
     parser.add_argument('--lossType', help="supervised loss", choices=['mean_l1'], default="mean_l1", type=str)
     parser.add_argument("--decayStep", help="accepted for compatibility: the reference never applies its decayed rate", type=int, default=500000)

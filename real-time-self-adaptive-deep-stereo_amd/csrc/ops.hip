@@ -1183,6 +1183,243 @@ extern "C" int mh_u8_to_f32(const uint8_t* in, float* out, int64_t n, void* stre
     return mh_check_launch("u8_to_f32");
 }
 
+// ---- Train.py's input side on the device (mh_frame_prepare): crop window + preprocessing.augment (Data_utils/preprocessing.py:31-89) + cast ----------------------
+// The host uploads the decoded 8-bit frames as they are; sample b's window is cut out of its own source (zeros outside: the centre pad) and augmented with the
+// fp32 operations of Data_utils/data_reader.augment in their order, UN-contracted (an fma would round once where numpy rounds twice): per pixel the result is the
+// host's bit for bit, only the contrast mean is summed in another order (float64, two stages, fixed order).  A lane owns 4 consecutive window pixels = 12 source
+// bytes (3 words where the address allows) = 3 float4 of each view and 1 float4 of the ground truth.
+#if defined(__clang__)
+#define MH_FP_EXACT _Pragma("clang fp contract(off)")
+#else
+#define MH_FP_EXACT
+#endif
+#define FP_SUM_PX 4096          // window pixels per workgroup of the partial-sum launch: 256 lanes x 4 quads of 4 pixels
+
+struct FrameArgs { const mh_frame_seg* segs; float* left; float* right; float* gt; double* ws; int H, W, npix, nblk; };
+
+// window pixels p0 .. p0+3 (p0 = y * W + x, p0 % 4 == 0, p0 < npix) of a uint8 [Hs][Ws][3] source -> 12 floats; 0 outside the source and past the window
+__device__ __forceinline__ void frame_load4(const unsigned char* __restrict__ src, int Hs, int Ws, int r0, int c0, int W, int npix, int p0, int y, int x,
+                                            float (&v)[12]) {
+    const int sy = r0 + y, sx = c0 + x;
+    if (x + 4 <= W && sy >= 0 && sy < Hs && sx >= 0 && sx + 4 <= Ws) {          // the four pixels are neighbours in one source row
+        const unsigned char* q = src + ((int64_t)sy * Ws + sx) * 3;
+        if ((((uintptr_t)q) & 3u) == 0) {
+            const unsigned* q4 = reinterpret_cast<const unsigned*>(q);
+            const unsigned w[3] = {q4[0], q4[1], q4[2]};
+#pragma unroll
+            for (int k = 0; k < 3; ++k) {
+                v[4 * k + 0] = (float)(w[k] & 0xffu); v[4 * k + 1] = (float)((w[k] >> 8) & 0xffu);
+                v[4 * k + 2] = (float)((w[k] >> 16) & 0xffu); v[4 * k + 3] = (float)(w[k] >> 24);
+            }
+        } else {
+#pragma unroll
+            for (int k = 0; k < 12; ++k) v[k] = (float)q[k];
+        }
+        return;
+    }
+    int yy = y, xx = x;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        while (xx >= W) { xx -= W; ++yy; }
+        const int ty = r0 + yy, tx = c0 + xx;
+        const bool in = p0 + j < npix && ty >= 0 && ty < Hs && tx >= 0 && tx < Ws;
+        const unsigned char* q = src + ((int64_t)(in ? ty : 0) * Ws + (in ? tx : 0)) * 3;
+        v[3 * j + 0] = in ? (float)q[0] : 0.f; v[3 * j + 1] = in ? (float)q[1] : 0.f; v[3 * j + 2] = in ? (float)q[2] : 0.f;
+        ++xx;
+    }
+}
+
+// the ground truth of the same four pixels: float32, or uint16 / 256 (the KITTI disparity PNG; a division by a power of two: exact)
+__device__ __forceinline__ void frame_load4_gt(const void* __restrict__ src, int kind, int Hs, int Ws, int r0, int c0, int W, int npix, int p0, int y, int x,
+                                               float (&g)[4]) {
+    const int sy = r0 + y, sx = c0 + x;
+    if (x + 4 <= W && sy >= 0 && sy < Hs && sx >= 0 && sx + 4 <= Ws) {
+        const int64_t e = (int64_t)sy * Ws + sx;
+        if (kind) {
+            const unsigned short* q = (const unsigned short*)src + e;
+            if ((((uintptr_t)q) & 7u) == 0) {
+                const uint2 w = *reinterpret_cast<const uint2*>(q);
+                g[0] = (float)(w.x & 0xffffu) * (1.0f / 256.0f); g[1] = (float)(w.x >> 16) * (1.0f / 256.0f);
+                g[2] = (float)(w.y & 0xffffu) * (1.0f / 256.0f); g[3] = (float)(w.y >> 16) * (1.0f / 256.0f);
+            } else {
+#pragma unroll
+                for (int j = 0; j < 4; ++j) g[j] = (float)q[j] * (1.0f / 256.0f);
+            }
+        } else {
+            const float* q = (const float*)src + e;
+            if ((((uintptr_t)q) & 15u) == 0) {
+                const float4 w = *reinterpret_cast<const float4*>(q);
+                g[0] = w.x; g[1] = w.y; g[2] = w.z; g[3] = w.w;
+            } else {
+#pragma unroll
+                for (int j = 0; j < 4; ++j) g[j] = q[j];
+            }
+        }
+        return;
+    }
+    int yy = y, xx = x;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        while (xx >= W) { xx -= W; ++yy; }
+        const int ty = r0 + yy, tx = c0 + xx;
+        const bool in = p0 + j < npix && ty >= 0 && ty < Hs && tx >= 0 && tx < Ws;
+        const int64_t e = in ? (int64_t)ty * Ws + tx : 0;
+        g[j] = !in ? 0.f : kind ? (float)((const unsigned short*)src)[e] * (1.0f / 256.0f) : ((const float*)src)[e];
+        ++xx;
+    }
+}
+
+// one colour of tf.image.adjust_hue's way back: k = (6 h + off) mod 6 (6 h + off < 12), v - v s clip(min(k, 4 - k), 0, 1)
+__device__ __forceinline__ float frame_hsv_channel(float h, float off, float v, float vs) {
+    MH_FP_EXACT
+    float k = h * 6.0f + off;
+    k = k >= 6.0f ? k - 6.0f : k;                       // == fmodf(k, 6): exact
+    const float t = fminf(fmaxf(fminf(k, 4.0f - k), 0.0f), 1.0f);
+    return v - vs * t;
+}
+
+// preprocessing.augment on one pixel, as Data_utils/data_reader.augment states it; m = the three channel means of this view (read only with bit 1)
+__device__ __forceinline__ void frame_augment(float& r, float& g, float& b, int active, float delta, float contrast, float hue, const float* m) {
+    MH_FP_EXACT
+    if (active & 1) { r = r + delta; g = g + delta; b = b + delta; }
+    if (active & 2) {
+        const float m0 = m[0], m1 = m[1], m2 = m[2];
+        r = (r - m0) * contrast + m0; g = (g - m1) * contrast + m1; b = (b - m2) * contrast + m2;
+    }
+    if (active & 4) {
+        const float mx = fmaxf(fmaxf(r, g), b), mn = fminf(fminf(r, g), b);
+        const float d = mx - mn;
+        const float s = mx > 0.f ? d / mx : 0.f;
+        const float dd = d > 0.f ? d : 1.f;
+        float h = (mx == r ? g - b : (mx == g ? b - r : r - g)) / dd;       // (one division: the three quotients of the host statement, selected first)
+        h = mx == r ? h : (mx == g ? 2.0f + h : 4.0f + h);
+        h = h / 6.0f;
+        h = d > 0.f ? h - floorf(h) : 0.f;              // numpy's x % 1.0 for x > -1
+        h = h + hue;
+        h = h - floorf(h);
+        const float vs = mx * s;
+        r = frame_hsv_channel(h, 5.0f, mx, vs); g = frame_hsv_channel(h, 3.0f, mx, vs); b = frame_hsv_channel(h, 1.0f, mx, vs);
+    }
+    r = fminf(fmaxf(r, 0.f), 255.f); g = fminf(fmaxf(g, 0.f), 255.f); b = fminf(fmaxf(b, 0.f), 255.f);
+}
+
+// first launch (only with contrast): grid (nblk, 2 B); workgroup (i, 2 b + view) sums FP_SUM_PX window pixels of one view after the brightness step, per channel
+__global__ __launch_bounds__(256) void frame_sums_kernel(FrameArgs a) {
+    __shared__ double red[3][256];
+    const int b = blockIdx.y >> 1, view = blockIdx.y & 1;
+    const mh_frame_seg s = a.segs[b];
+    if (!(s.active & 2)) return;                         // workgroup-uniform: nobody reads this sample's partial sums
+    const unsigned char* src = (const unsigned char*)(view ? s.right : s.left);
+    const bool bright = (s.active & 1) != 0;
+    double acc[3] = {0.0, 0.0, 0.0};
+    for (int i = 0; i < FP_SUM_PX / 1024; ++i) {
+        const int p0 = ((int)blockIdx.x * (FP_SUM_PX / 4) + i * 256 + (int)threadIdx.x) * 4;
+        if (p0 >= a.npix) break;
+        const int y = p0 / a.W, x = p0 - y * a.W;
+        float v[12];
+        frame_load4(src, s.Hs, s.Ws, s.r0, s.c0, a.W, a.npix, p0, y, x, v);
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+            if (p0 + j < a.npix) {
+#pragma unroll
+                for (int c = 0; c < 3; ++c) acc[c] += (double)(bright ? v[3 * j + c] + s.delta : v[3 * j + c]);
+            }
+    }
+    red[0][threadIdx.x] = acc[0]; red[1][threadIdx.x] = acc[1]; red[2][threadIdx.x] = acc[2];
+    __syncthreads();
+    for (int o = 128; o > 0; o >>= 1) {
+        if ((int)threadIdx.x < o) {
+            red[0][threadIdx.x] += red[0][threadIdx.x + o];
+            red[1][threadIdx.x] += red[1][threadIdx.x + o];
+            red[2][threadIdx.x] += red[2][threadIdx.x + o];
+        }
+        __syncthreads();
+    }
+    if (threadIdx.x < 3) a.ws[((int64_t)blockIdx.y * a.nblk + blockIdx.x) * 3 + threadIdx.x] = red[threadIdx.x][0];
+}
+
+// the applying launch: grid (ceil(npix / 1024), B).  With contrast every workgroup first finishes its sample's six sums (view x channel) from the partial sums,
+// 32 lanes per sum, in a fixed order.
+__global__ __launch_bounds__(256) void frame_apply_kernel(FrameArgs a) {
+    __shared__ double red[6][32];
+    __shared__ float mean[6];
+    const int b = blockIdx.y, t = threadIdx.x;
+    const mh_frame_seg s = a.segs[b];
+    const bool poison = (s.active & 2) && !a.ws;        // contrast without the partial sums: the caller broke its word -- say so in the result
+    if ((s.active & 2) && a.ws) {
+        const int j = t >> 5, l = t & 31;               // j = 3 * view + channel
+        if (t < 192) {
+            const double* part = a.ws + ((int64_t)(2 * b + j / 3) * a.nblk) * 3 + j % 3;
+            double acc = 0.0;
+            for (int i = l; i < a.nblk; i += 32) acc += part[(int64_t)i * 3];
+            red[j][l] = acc;
+        }
+        __syncthreads();
+        for (int o = 16; o > 0; o >>= 1) {
+            if (t < 192 && l < o) red[j][l] += red[j][l + o];
+            __syncthreads();
+        }
+        if (t < 6) mean[t] = (float)(red[t][0] / (double)a.npix);
+        __syncthreads();
+    }
+    const int p0 = ((int)blockIdx.x * 256 + t) * 4;
+    if (p0 >= a.npix) return;
+    const int y = p0 / a.W, x = p0 - y * a.W;
+    const bool full = p0 + 4 <= a.npix;
+#pragma unroll
+    for (int view = 0; view < 2; ++view) {
+        float v[12];
+        frame_load4((const unsigned char*)(view ? s.right : s.left), s.Hs, s.Ws, s.r0, s.c0, a.W, a.npix, p0, y, x, v);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) frame_augment(v[3 * j], v[3 * j + 1], v[3 * j + 2], s.active, s.delta, s.contrast, s.hue, mean + 3 * view);
+        if (poison) {
+#pragma unroll
+            for (int k = 0; k < 12; ++k) v[k] = __builtin_nanf("");
+        }
+        float* dst = (view ? a.right : a.left) + ((int64_t)b * a.npix + p0) * 3;
+        if (full && (((uintptr_t)dst) & 15u) == 0) {
+#pragma unroll
+            for (int k = 0; k < 3; ++k) reinterpret_cast<float4*>(dst)[k] = make_float4(v[4 * k], v[4 * k + 1], v[4 * k + 2], v[4 * k + 3]);
+        } else {
+#pragma unroll
+            for (int k = 0; k < 12; ++k) if (p0 + k / 3 < a.npix) dst[k] = v[k];
+        }
+    }
+    float g[4];
+    frame_load4_gt(s.gt, s.gt_kind, s.Hs, s.Ws, s.r0, s.c0, a.W, a.npix, p0, y, x, g);
+    float* dst = a.gt + (int64_t)b * a.npix + p0;
+    if (full && (((uintptr_t)dst) & 15u) == 0) {
+        *reinterpret_cast<float4*>(dst) = make_float4(g[0], g[1], g[2], g[3]);
+    } else {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) if (p0 + j < a.npix) dst[j] = g[j];
+    }
+}
+
+static inline int frame_sum_blocks(int64_t npix) { return (int)((npix + FP_SUM_PX - 1) / FP_SUM_PX); }
+
+extern "C" int64_t mh_frame_prepare_ws_floats(int32_t B, int32_t H, int32_t W) {
+    if (B <= 0 || H <= 0 || W <= 0) return 0;
+    return 2 * ((int64_t)B * 2 * frame_sum_blocks((int64_t)H * W) * 3);            // float64 partial sums: [B][view][workgroup][channel]
+}
+
+extern "C" int mh_frame_prepare(const mh_frame_seg* segs, int32_t B, int32_t H, int32_t W, float* left, float* right, float* gt, float* ws, void* stream) {
+    MH_REQUIRE(segs && left && right && gt, MH_ERR_ARG, "mh_frame_prepare: null argument");
+    MH_REQUIRE(B > 0 && H > 0 && W > 0, MH_ERR_ARG, "mh_frame_prepare: bad dimension");
+    MH_REQUIRE((int64_t)H * W * 3 < (1ll << 31) && 2 * (int64_t)B < 65536, MH_ERR_UNSUPPORTED, "mh_frame_prepare: window or batch too large");
+    MH_REQUIRE((((uintptr_t)ws) & 7u) == 0, MH_ERR_ALIGN, "mh_frame_prepare: ws must be 8-byte aligned");
+    FrameArgs a{};
+    a.segs = segs; a.left = left; a.right = right; a.gt = gt; a.ws = (double*)ws;
+    a.H = H; a.W = W; a.npix = H * W; a.nblk = frame_sum_blocks(a.npix);
+    if (ws) {
+        hipLaunchKernelGGL(frame_sums_kernel, dim3((unsigned)a.nblk, (unsigned)(2 * B)), dim3(256), 0, (hipStream_t)stream, a);
+        if (int e = mh_check_launch("frame_sums")) return e;
+    }
+    hipLaunchKernelGGL(frame_apply_kernel, dim3((unsigned)((a.npix + 1023) / 1024), (unsigned)B), dim3(256), 0, (hipStream_t)stream, a);
+    mh_note_kernel("frame_apply_kernel grid %d x %d, %d launch%s", (a.npix + 1023) / 1024, B, ws ? 2 : 1, ws ? "es" : "");
+    return mh_check_launch("frame_apply");
+}
+
 extern "C" int mh_resize_image_fwd(const float* in, float* out, int32_t B, int32_t Hi, int32_t Wi, int32_t C, int32_t Ho, int32_t Wo,
                                    void* stream) {
     MH_REQUIRE(in && out && B > 0 && Hi > 0 && Wi > 0 && C > 0 && Ho > 0 && Wo > 0, MH_ERR_ARG, "mh_resize_image_fwd: bad argument");

@@ -486,6 +486,68 @@ def fetch_inputs(lib, table_ptr, dsts, stream=None):
     lib.fetch_inputs(C.c_void_p(table_ptr), dp, cnt, n, _p(stream))
 
 
+class FrameTable(object):
+    """The per-sample table of mh_frame_prepare (B x mh_frame_seg), like InputTable page-locked host memory the device reads through its device-side address: the
+    host fills it without an API call; it must stay as it is until the call that reads it has run.  segs[b] = the ctypes record of sample b."""
+
+    def __init__(self, lib, device, B, pinned=True):
+        """pinned=False: plain host memory -- frame_prepare then reads a device copy made on the current stream (one-off calls: nothing to keep alive)"""
+        cuda = torch.device(device).type == "cuda"
+        self.B, self.device = int(B), torch.device(device)
+        self.buf = torch.zeros(C.sizeof(_ffi.FrameSeg) * self.B, dtype=torch.uint8, pin_memory=cuda and pinned)
+        self.segs = (_ffi.FrameSeg * self.B).from_address(self.buf.data_ptr())
+        if cuda and not pinned:
+            self.ptr = None
+        elif cuda:
+            dp = C.c_void_p()
+            lib.host_device_pointer(C.c_void_p(self.buf.data_ptr()), C.byref(dp))
+            self.ptr = dp.value
+        else:
+            self.ptr = self.buf.data_ptr()
+
+    @classmethod
+    def at(cls, host_address, device_address, B):
+        """a table laid over memory the caller owns: B records at host_address, which the device will see at device_address (a staging buffer the caller
+        copies up in front of the call)"""
+        self = cls.__new__(cls)
+        self.B, self.device, self.buf = int(B), None, None
+        self.segs = (_ffi.FrameSeg * self.B).from_address(host_address)
+        self.ptr = device_address
+        return self
+
+    def set(self, b, left, right, gt, Hs, Ws, r0, c0, gt_kind, active=0, delta=0.0, contrast=1.0, hue=1.0):
+        """left / right / gt: device addresses of sample b's uint8 [Hs,Ws,3] frames and its [Hs,Ws] ground truth (gt_kind 0 float32, 1 uint16 / 256)"""
+        s = self.segs[b]
+        s.left, s.right, s.gt = left, right, gt
+        s.Hs, s.Ws, s.r0, s.c0, s.gt_kind, s.active = int(Hs), int(Ws), int(r0), int(c0), int(gt_kind), int(active)
+        s.delta, s.contrast, s.hue = float(delta), float(contrast), float(hue)
+
+    def any_contrast(self):
+        return any(self.segs[b].active & 2 for b in range(self.B))
+
+
+def frame_prepare_ws(lib, B, H, W, device):
+    """the partial-sum workspace of frame_prepare (float64 sums in a float32 tensor: torch allocations are 8-byte aligned)"""
+    return torch.empty(int(lib.frame_prepare_ws_floats(B, H, W)), dtype=torch.float32, device=device)
+
+
+def frame_prepare(lib, table, left, right, gt, ws=None, stream=None):
+    """left, right [B,H,W,3], gt [B,H,W,1] (float32, contiguous, written in every element) <- the windows the FrameTable names, cropped, augmented and cast
+    (mh_frame_prepare).  ws: frame_prepare_ws(...); needed only when a sample has the contrast bit set (without it the call is one launch)."""
+    B, H, W, _ = left.shape
+    assert table.B == B and tuple(right.shape) == (B, H, W, 3) and tuple(gt.shape) == (B, H, W, 1)
+    assert all(t.dtype == torch.float32 and t.is_contiguous() for t in (left, right, gt))
+    if table.any_contrast():
+        assert ws is not None and ws.numel() >= lib.frame_prepare_ws_floats(B, H, W), "frame_prepare: a sample has the contrast bit set: pass ws"
+    else:
+        ws = None
+    ptr = table.ptr
+    if ptr is None:
+        copy = table.buf.to(table.device)          # freed in stream order behind the launch
+        ptr = copy.data_ptr()
+    lib.frame_prepare(C.c_void_p(ptr), B, H, W, _p(left), _p(right), _p(gt), _p(ws), _p(stream))
+
+
 def shadow_cast(lib, pairs, device, keep, stream=None):
     """pairs: [(View src, Shadow dst)] -> every dst = bf16(src), ONE launch (mh_shadow_cast).  `keep` keeps the device table alive."""
     if not pairs:
