@@ -406,6 +406,20 @@ int64_t mh_frame_prepare_ws_floats(int32_t B, int32_t H, int32_t W);
 int mh_frame_prepare(const mh_frame_seg* segs, int32_t B, int32_t H, int32_t W,
                      float* left, float* right, float* gt, float* ws, void* stream);
 
+/* ---- proxy labels of the continual loop from an on-device matcher: replaces the proxy column of continual_data_reader (README.MD:59-61 of the reference:
+ *      "proxy labels ... computed with a traditional stereo algorithm" offline, one 16-bit PNG per frame).  Census 9 x 7 on the gray frames
+ *      (77 R + 150 G + 29 B + 128 >> 8, replicate border), Hamming cost for d = 0 .. D-1 (64 where x - d < 0), four-path semi-global aggregation (left->right,
+ *      right->left, top->bottom, bottom->top; penalties p1 / p2), winner = lowest d of the smallest sum, uniqueness (rejected when uniq * s2 < 100 * s1,
+ *      s2 = the smallest sum with |d - d1| > 1), left-right check against the right view's winner read off the same volume (|dR(x - d1) - d1| <= lr_tol;
+ *      d1 == 0 and x - d1 < 0 are rejected), parabola sub-pixel (one float32 division, one float32 add).  left, right: [B,H,W,3] uint8 (frames_u8 != 0) or
+ *      float32 holding 0..255 (rounded to nearest, clamped); proxy: [B,H,W] float32, every element written, 0 = rejected (the proxy loss's `proxy <= 0`).
+ *      Integer arithmetic up to the sub-pixel step and no atomics: two calls give the same bits.  ws: mh_sgm_ws_bytes bytes, 16-byte aligned (census words,
+ *      one uint8 volume per path, the right view's winners).  H >= 7, W >= 9 (W < D is legal), D = 64, 128 or 192, 0 < p1 <= p2 <= 191, 0 < uniq <= 100,
+ *      lr_tol >= 0, B * H * W < 2^31 - 256, B < 32768.  Four launches on `stream`; never part of a plan. */
+int64_t mh_sgm_ws_bytes(int32_t B, int32_t H, int32_t W, int32_t D);
+int mh_sgm_proxy(const void* left, const void* right, int32_t frames_u8, void* ws, float* proxy,
+                 int32_t B, int32_t H, int32_t W, int32_t D, int32_t p1, int32_t p2, int32_t uniq, int32_t lr_tol, void* stream);
+
 /* ---- preprocessing.pad_image (REFLECT, preprocessing.py:7-29) fused with the float cast
  *      and the channel padding 3 -> out_ld (extra channels zero) ------------------------ */
 /* out = in / div - sub  (MADNet: div=1, sub=0; DispNet._preprocess_inputs, DispNet.py:59-73: x/255 - 100/255) */

@@ -1,7 +1,8 @@
 """List reader of the continual-adaptation driver: rows `left,right,gt,proxy` separated by ',' or ';', '#' lines skipped
 (Data_utils/continual_data_reader.py:55-78); frames are centre-cropped / zero-padded to crop_shape
 (tf.image.resize_image_with_crop_or_pad, :150), gt and proxy cut to the left image's width first (:137,146); 16-bit
-PNGs are value/256 (:128-133,139-144).  Yields (left, right, gt, proxy, real_width) with [1,H,W,C] float32 arrays."""
+PNGs are value/256 (:128-133,139-144).  Yields (left, right, gt, proxy, real_width) with [1,H,W,C] float32 arrays; dataset(proxies=False) takes rows
+`left,right,gt`, reads no proxy file and yields (left, right, gt, real_width)."""
 import re
 
 import numpy as np
@@ -29,7 +30,12 @@ class dataset(object):
         if batch_size != 1 or augment or is_training or shuffle:
             raise NotImplementedError('continual adaptation reads frames in order, batch 1, no augmentation')
         l, r, g, p = read_list_file(path_file)
-        if not (len(l) == len(r) == len(g) == len(p)):
+        if not proxies:
+            # the proxy labels come from somewhere else (--proxies sgm: the on-device matcher): rows left,right,gt; a fourth column is not read
+            if not (len(l) == len(r) == len(g)):
+                raise Exception('Expected rows left,right,gt')
+            p = [None] * len(l)
+        elif not (len(l) == len(r) == len(g) == len(p)):
             raise Exception('Expected rows left,right,gt,proxy')
         self._couples = list(zip(l, r, g, p))
         self._crop, self._epochs = tuple(crop_shape), num_epochs
@@ -47,5 +53,8 @@ class dataset(object):
                 left = _read_image(l); right = _read_image(r)
                 real_width = left.shape[1]
                 gt = _read_image(g, True)[:, :real_width]
+                if p is None:                       # proxies=False: (left, right, gt, real_width)
+                    yield tuple(center_crop_or_pad(a, th, tw)[None] for a in (left, right, gt)) + (np.float32(real_width),)
+                    continue
                 px = _read_image(p, True)[:, :real_width]
                 yield tuple(center_crop_or_pad(a, th, tw)[None] for a in (left, right, gt, px)) + (np.float32(real_width),)

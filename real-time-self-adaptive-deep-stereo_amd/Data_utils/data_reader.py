@@ -416,10 +416,16 @@ class device_prefetcher(object):
 
     POLL = 2e-4            # seconds between two looks of a reader that is out of slots
 
-    def __init__(self, data_set, device='cuda', depth=3, consumer_stream=None, lib=None, cast=True):
+    def __init__(self, data_set, device='cuda', depth=3, consumer_stream=None, lib=None, cast=True, proxy_matcher=None):
         """uint8 arrays from the data set are uploaded as uint8; cast=True: cast to float32 on the GPU (mh_u8_to_f32 on the copy stream; `lib` = the loaded
         library, default the product's) so that the consumer always sees float32 tensors; cast=False: yielded as uint8 device tensors (Adapter.step casts
-        while it copies them into the engine's input buffers: one kernel and 5.6 MB of traffic less per image)."""
+        while it copies them into the engine's input buffers: one kernel and 5.6 MB of traffic less per image).
+        proxy_matcher: a madnet_hip.proxy.ProxyMatcher for the frames' shape.  Every slot then carries a proxy disparity map [B,H,W] of its own, computed
+        from the slot's left / right frames on the copy stream, behind their upload and in front of the slot's ready event (where mh_frame_prepare runs for
+        the training input): it overlaps the previous step and the consumer needs no further synchronisation.  The iterator yields it in the proxy
+        position, (left, right, gt, proxy, *rest)."""
+        self._matcher = proxy_matcher
+        self._proxy = None                       # per slot: the matcher's output
         self._lib = lib
         import collections
         import queue
@@ -520,6 +526,10 @@ class device_prefetcher(object):
                 stage = [t.empty(np.shape(a), dtype=t.uint8, device=self._dev) if q else None for a, q in zip(arrays, u8)]
                 devb = [(s8 if (q and not self._cast) else t.empty(np.shape(a), dtype=t.float32, device=self._dev)) for a, q, s8 in zip(arrays, u8, stage)]
                 self._ring.append((host, devb, t.cuda.Event() if self._cuda else None, stage, t.cuda.Event() if self._cuda else None))
+            if self._matcher is not None:
+                if len(arrays) < 3 or tuple(np.shape(arrays[0])) != tuple(self._matcher.shape) + (3,) or np.shape(arrays[1]) != np.shape(arrays[0]):
+                    raise ValueError("proxy_matcher: built for frames %s, the data set yields %s" % (self._matcher.shape, np.shape(arrays[0])))
+                self._proxy = [self._matcher.new_output() for _ in self._ring]
             self._free = list(range(len(self._ring)))[::-1]
         while not self._free:
             try:
@@ -541,6 +551,8 @@ class device_prefetcher(object):
                 if self._stop.is_set():
                     return
                 if isinstance(arrays, raw_batch):        # dataset(prepare='device'): crop, augment and cast on the device
+                    if self._matcher is not None:
+                        raise ValueError("proxy_matcher works on uploaded frames, not on dataset(prepare='device') batches")
                     i = self._upload_raw(arrays)
                     if i is None:
                         return
@@ -561,6 +573,8 @@ class device_prefetcher(object):
                                 s8.copy_(h, non_blocking=True)
                                 if self._cast:
                                     self._lib.u8_to_f32(s8.data_ptr(), d.data_ptr(), s8.numel(), self._copy_stream.cuda_stream)
+                        if self._matcher is not None:
+                            self._matcher.compute(devb[0], devb[1], out=self._proxy[i], stream=self._copy_stream.cuda_stream)
                         ev.record(self._copy_stream)
                 else:
                     for h, d, s8 in zip(host, devb, stage):
@@ -570,6 +584,8 @@ class device_prefetcher(object):
                             s8.copy_(h)
                             if self._cast and self._lib is not None:
                                 self._lib.u8_to_f32(s8.data_ptr(), d.data_ptr(), s8.numel(), None)
+                    if self._matcher is not None:
+                        self._matcher.compute(devb[0], devb[1], out=self._proxy[i])
                 self._q.put(i)
             self._q.put(None)
         except Exception as e:                   # surface reader errors in the consumer
@@ -595,6 +611,9 @@ class device_prefetcher(object):
             if self._cuda and not ev.query():        # (uploads run a step ahead: usually complete -- no cross-stream edge in front of the step then)
                 (self._consumer or self._torch.cuda.current_stream(self._dev)).wait_event(ev)
             prev = i
+            if self._proxy is not None:
+                yield tuple(devb[:3]) + (self._proxy[i],) + tuple(devb[3:])
+                continue
             yield tuple(devb)
 
     def close(self):

@@ -3,7 +3,8 @@ series.csv, histogram.csv, params.sh, config.json, disparities/*.png, weights/mo
 (Stereo_Continual_Adaptation.py:30-345).  Differences of the loop to Stereo_Online_Adaptation: the loss is the
 proxy-label mean_l1 (weight 0.01 full / 0.1 per MAD block, :75,112), the weights are only updated every --dilation
 frames (:205), the reward update uses --decay / --uf (:218-221), the report is EPE + D1 (:241-249).
-The per-frame device work is madnet_hip.adapter.Adapter.step(left, right, gt, proxy)."""
+The per-frame device work is madnet_hip.adapter.Adapter.step(left, right, gt, proxy).  --proxies sgm computes the proxy labels on the device
+(madnet_hip.proxy.ProxyMatcher over mh_sgm_proxy) instead of reading the list's fourth column."""
 import argparse
 import json
 import os
@@ -39,7 +40,7 @@ def main(args):
     with open(args.blockConfig) as json_data:
         train_config = json.load(json_data)
     data_set = continual_data_reader.dataset(args.list, batch_size=1, crop_shape=args.imageShape, num_epochs=1,
-                                             augment=False, is_training=False, proxies=True, shuffle=False)
+                                             augment=False, is_training=False, proxies=args.proxies != 'sgm', shuffle=False)
     H, W = args.imageShape
     dev = 'cuda'
     net_args = {'left_img': torch.zeros(1, H, W, 3, device=dev), 'right_img': torch.zeros(1, H, W, 3, device=dev),
@@ -58,9 +59,14 @@ def main(args):
     with open(os.path.join(args.output, 'histogram.csv'), 'w') as f_out:
         f_out.write('Histogram\n')
     try:
-        frames = data_reader.device_prefetcher(data_set, dev, depth=3, consumer_stream=adapter.stream, cast=False)
+        matcher = None
+        if args.proxies == 'sgm':
+            # the proxy labels of every frame from the frame itself: census + semi-global matching on the prefetcher's upload stream (madnet_hip/proxy.py)
+            from madnet_hip.proxy import ProxyMatcher
+            matcher = ProxyMatcher(adapter.lib, 1, H, W, max_disp=args.proxyMaxDisp, device=dev)
+        frames = data_reader.device_prefetcher(data_set, dev, depth=3, consumer_stream=adapter.stream, cast=False, proxy_matcher=matcher)
         for left, right, gt, proxy, real_width in frames:
-            out = adapter.step(left, right, gt[..., 0], proxy=proxy[..., 0])
+            out = adapter.step(left, right, gt[..., 0], proxy=proxy if matcher is not None else proxy[..., 0])
             d1, epe = out['d1'], out['epe_gt0']          # computed inside the step (mh_metrics_kitti): the loop launches nothing and waits for nothing of its own
             d1_accumulator.append(d1)
             avg_accumulator.append(epe)
@@ -126,6 +132,8 @@ def build_parser():
     parser.add_argument("--decay", help="multiplicative decay of the sampling logits", type=float, default=0.99)
     parser.add_argument("--uf", help="gain of the reward added to the logits of the last trained portions", type=float, default=0.01)
     parser.add_argument("--precision", help="MFMA arithmetic of the conv kernels: fp32 (default; the reference adapts in fp32), mixed (forward within fp32 tolerance, bf16 gradients) or bf16 (opt-in throughput mode)", choices=['fp32', 'mixed', 'bf16'], default='fp32')
+    parser.add_argument("--proxies", help="where the proxy labels come from: list = the fourth column of the list (disparity PNGs of an external matcher); sgm = computed on the GPU from every frame pair (census + four-path semi-global matching), the list then needs only left,right,gt", choices=['list', 'sgm'], default='list')
+    parser.add_argument("--proxyMaxDisp", help="--proxies sgm: number of disparities searched (64, 128 or 192)", type=int, default=128)
     parser.add_argument("--dumpOutputs", help="also write the float32 disparity of every frame to <output>/disparities/disparity_<step>.npy", action='store_true')
     return parser
 

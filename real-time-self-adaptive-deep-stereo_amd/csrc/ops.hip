@@ -1420,6 +1420,235 @@ extern "C" int mh_frame_prepare(const mh_frame_seg* segs, int32_t B, int32_t H, 
     return mh_check_launch("frame_apply");
 }
 
+// ---- proxy labels of the continual loop on the device (mh_sgm_proxy): census + four-path semi-global matching ---------------------------------------------------
+// Replaces the proxy column of the continual list (an external matcher's PNGs).  Integer arithmetic up to the sub-pixel step, no atomics, every launch writes
+// what the next one reads: the result does not depend on launch shape or order.  Workspace: census words [2][B][H][W] (8 bytes), one uint8 volume [B][H][W][D]
+// per path (L_r <= 64 + p2 <= 255), the right view's winner [B][H][W] (uint8).  The matching cost is never stored: a path step recomputes
+// popcount(cL(y, x) ^ cR(y, x - d)) from the census rows (16 bytes per pixel and view instead of a D-byte volume read by four paths).
+#define SGM_BIG (1 << 20)
+#define SGM_CT_W 32             // census tile: 32 x 8 pixels per workgroup, halo 4 x 3
+#define SGM_CT_H 8
+
+struct SgmArgs {
+    const void* left; const void* right;
+    unsigned long long* census; unsigned char* vol; unsigned char* dr; float* out;
+    int64_t vstride;            // bytes between two path volumes
+    int B, H, W, D, u8, p1, p2, uniq, lr_tol, npix;
+};
+
+// integers through the float shuffle (the bits travel unchanged); the mask may differ per lane
+__device__ __forceinline__ int sgm_shfl_xor(int v, int mask) { return __builtin_bit_cast(int, __shfl_xor(__builtin_bit_cast(float, v), mask)); }
+__device__ __forceinline__ int sgm_wave_min(int v) {
+    v = min(v, sgm_shfl_xor(v, 32)); v = min(v, sgm_shfl_xor(v, 16)); v = min(v, sgm_shfl_xor(v, 8));
+    v = min(v, sgm_shfl_xor(v, 4)); v = min(v, sgm_shfl_xor(v, 2)); v = min(v, sgm_shfl_xor(v, 1));
+    return v;
+}
+__device__ __forceinline__ int sgm_u8(float v) { return (int)fminf(fmaxf(floorf(v + 0.5f), 0.f), 255.f); }
+
+// gray + census 9 x 7 of both views: grid (tiles x, tiles y, 2 B), z = 2 b + view
+__global__ __launch_bounds__(256) void sgm_census_kernel(SgmArgs a) {
+    __shared__ int s_g[SGM_CT_H + 6][SGM_CT_W + 8];
+    const int b = (int)blockIdx.z >> 1, view = (int)blockIdx.z & 1;
+    const int x0 = (int)blockIdx.x * SGM_CT_W, y0 = (int)blockIdx.y * SGM_CT_H;
+    const void* src = view ? a.right : a.left;
+    const int64_t frame = (int64_t)b * a.H * a.W;
+    for (int i = threadIdx.x; i < (SGM_CT_H + 6) * (SGM_CT_W + 8); i += 256) {
+        const int ty = i / (SGM_CT_W + 8), tx = i - ty * (SGM_CT_W + 8);
+        const int y = min(max(y0 + ty - 3, 0), a.H - 1), x = min(max(x0 + tx - 4, 0), a.W - 1);
+        const int64_t e = (frame + (int64_t)y * a.W + x) * 3;
+        int r, g, bl;
+        if (a.u8) {
+            const unsigned char* q = (const unsigned char*)src + e;
+            r = q[0]; g = q[1]; bl = q[2];
+        } else {
+            const float* q = (const float*)src + e;
+            r = sgm_u8(q[0]); g = sgm_u8(q[1]); bl = sgm_u8(q[2]);
+        }
+        s_g[ty][tx] = (77 * r + 150 * g + 29 * bl + 128) >> 8;
+    }
+    __syncthreads();
+    const int tx = threadIdx.x & (SGM_CT_W - 1), ty = threadIdx.x / SGM_CT_W;
+    const int x = x0 + tx, y = y0 + ty;
+    if (x >= a.W || y >= a.H) return;
+    const int c = s_g[ty + 3][tx + 4];
+    unsigned w0 = 0, w1 = 0;
+    int k = 0;
+#pragma unroll
+    for (int dy = 0; dy < 7; ++dy) {
+#pragma unroll
+        for (int dx = 0; dx < 9; ++dx) {
+            if (dy == 3 && dx == 4) continue;
+            const unsigned bit = s_g[ty + dy][tx + dx] < c ? 1u : 0u;
+            if (k < 31) w0 = (w0 << 1) | bit; else w1 = (w1 << 1) | bit;
+            ++k;
+        }
+    }
+    a.census[(int64_t)view * a.npix + frame + (int64_t)y * a.W + x] = ((unsigned long long)w0 << 32) | w1;
+}
+
+// the costs of this lane's K disparities (d = K lane + k) at pixel x of a row: cl = the left word, cr = the right view's row
+template <int K>
+__device__ __forceinline__ void sgm_cost(const unsigned long long* __restrict__ cr, unsigned long long cl, int x, int lane, int (&c)[K]) {
+#pragma unroll
+    for (int k = 0; k < K; ++k) {
+        const int xr = x - (lane * K + k);
+        const int h = __builtin_popcountll(cl ^ cr[max(xr, 0)]);           // (the load is unconditional: nothing waits for it at a branch join)
+        c[k] = xr >= 0 ? h : 64;
+    }
+}
+
+// Aggregation, all four paths in one launch: grid (2 H + 2 W, B), one wave per path line -- a row left->right / right->left, a column top->bottom /
+// bottom->top --, K = D / 64 neighbouring disparities per lane: d -/+ 1 come from the neighbouring lane, m from a wave min.  Sequential along the line (the
+// step's chain is two shuffles + the six of the reduction), parallel across lines and paths; the next pixel's costs are fetched before the step.
+template <int K>
+__global__ __launch_bounds__(64) void sgm_paths_kernel(SgmArgs a) {
+    const int lane = threadIdx.x, b = blockIdx.y;
+    int line = blockIdx.x, path, y, x, dy = 0, dx = 0, n;
+    if (line < 2 * a.H) { path = line & 1; y = line >> 1; x = path ? a.W - 1 : 0; dx = path ? -1 : 1; n = a.W; }
+    else { line -= 2 * a.H; path = 2 + (line & 1); x = line >> 1; y = (line & 1) ? a.H - 1 : 0; dy = (line & 1) ? -1 : 1; n = a.H; }
+    const int64_t frame = (int64_t)b * a.H * a.W;
+    const unsigned long long* __restrict__ cl = a.census + frame;
+    const unsigned long long* __restrict__ cr = a.census + a.npix + frame;
+    unsigned char* __restrict__ vol = a.vol + (int64_t)path * a.vstride + frame * a.D + lane * K;
+    const int up_mask = lane < 63 ? (lane ^ (lane + 1)) : 0;           // lane ^ mask = lane + 1
+    int L[K], c[K], cn[K], m = 0;
+    sgm_cost<K>(cr + (int64_t)y * a.W, cl[(int64_t)y * a.W + x], x, lane, c);
+    for (int i = 0; i < n; ++i) {
+        const int yn = y + dy, xn = x + dx;
+        const int yf = min(max(yn, 0), a.H - 1), xf = min(max(xn, 0), a.W - 1);        // the line's last step fetches its own pixel again
+        sgm_cost<K>(cr + (int64_t)yf * a.W, cl[(int64_t)yf * a.W + xf], xf, lane, cn);
+        int mn = SGM_BIG;
+        if (i == 0) {
+#pragma unroll
+            for (int k = 0; k < K; ++k) { L[k] = c[k]; mn = min(mn, L[k]); }
+        } else {
+            int below = __shfl_up(L[K - 1], 1u), above = sgm_shfl_xor(L[0], up_mask);
+            if (lane == 0) below = SGM_BIG;                            // d - 1 < 0 and d + 1 > D - 1: absent
+            if (lane == 63) above = SGM_BIG;
+            int nl[K];
+#pragma unroll
+            for (int k = 0; k < K; ++k) {
+                const int lo = k ? L[k - 1] : below, hi = k < K - 1 ? L[k + 1] : above;
+                nl[k] = c[k] + min(min(L[k], min(lo, hi) + a.p1), m + a.p2) - m;
+                mn = min(mn, nl[k]);
+            }
+#pragma unroll
+            for (int k = 0; k < K; ++k) L[k] = nl[k];
+        }
+        m = sgm_wave_min(mn);
+        unsigned char* q = vol + ((int64_t)y * a.W + x) * a.D;
+        if (K == 2) *reinterpret_cast<unsigned short*>(q) = (unsigned short)(L[0] | (L[K - 1] << 8));
+        else {
+#pragma unroll
+            for (int k = 0; k < K; ++k) q[k] = (unsigned char)L[k];
+        }
+#pragma unroll
+        for (int k = 0; k < K; ++k) c[k] = cn[k];
+        y = yn; x = xn;
+    }
+}
+
+// S(pixel, d) = the sum of the four paths; p points at path 0's byte
+__device__ __forceinline__ int sgm_sum4(const unsigned char* __restrict__ p, int64_t vs) { return (int)p[0] + (int)p[vs] + (int)p[2 * vs] + (int)p[3 * vs]; }
+
+// the right view's winner from the same volume: dR(y, x') = argmin over d with x' + d < W of S(y, x' + d, d), lowest d on ties.  One lane per pixel walks the diagonal
+__global__ __launch_bounds__(256) void sgm_right_kernel(SgmArgs a) {
+    const int pix = (int)blockIdx.x * 256 + (int)threadIdx.x;
+    if (pix >= a.npix) return;
+    const int x = pix % a.W, nd = min(a.D, a.W - x);
+    const unsigned char* __restrict__ p = a.vol + (int64_t)pix * a.D;
+    int best = SGM_BIG, bd = 0;
+#pragma unroll 4
+    for (int d = 0; d < nd; ++d) {
+        const int s = sgm_sum4(p + (int64_t)d * (a.D + 1), a.vstride);
+        if (s < best) { best = s; bd = d; }
+    }
+    a.dr[pix] = (unsigned char)bd;
+}
+
+// winner, uniqueness, left-right check, sub-pixel: one wave per pixel (4 per workgroup), K disparities per lane.  Every pixel is written (0 = rejected)
+template <int K>
+__global__ __launch_bounds__(256) void sgm_select_kernel(SgmArgs a) {
+    const int lane = threadIdx.x & 63, pix = (int)blockIdx.x * 4 + ((int)threadIdx.x >> 6);
+    if (pix >= a.npix) return;                                          // wave-uniform
+    const unsigned char* __restrict__ p = a.vol + (int64_t)pix * a.D + lane * K;
+    int S[K], key = 0x7fffffff;
+#pragma unroll
+    for (int k = 0; k < K; ++k) { S[k] = sgm_sum4(p + k, a.vstride); key = min(key, (S[k] << 8) | (lane * K + k)); }      // S <= 1020, d < 256: lowest d on ties
+    key = sgm_wave_min(key);
+    const int d1 = key & 255, s1 = key >> 8;
+    int s2 = SGM_BIG, sm = SGM_BIG, sp = SGM_BIG;
+#pragma unroll
+    for (int k = 0; k < K; ++k) {
+        const int d = lane * K + k;
+        if (d < d1 - 1 || d > d1 + 1) s2 = min(s2, S[k]);
+        if (d == d1 - 1) sm = S[k];
+        if (d == d1 + 1) sp = S[k];
+    }
+    s2 = sgm_wave_min(s2); sm = sgm_wave_min(sm); sp = sgm_wave_min(sp);
+    if (lane) return;
+    bool ok = !(s2 < SGM_BIG && a.uniq * s2 < 100 * s1) && d1 != 0;
+    const int xr = pix % a.W - d1;
+    ok = ok && xr >= 0;
+    if (ok) { const int back = a.dr[pix - d1]; ok = abs(back - d1) <= a.lr_tol; }
+    float o = (float)d1;
+    if (d1 >= 1 && d1 <= a.D - 2) {
+        const int den = 2 * (sm + sp - 2 * s1);
+        if (den > 0) o = o + (float)(sm - sp) / (float)den;
+    }
+    a.out[pix] = ok ? o : 0.f;
+}
+
+static inline int64_t sgm_align16(int64_t n) { return (n + 15) / 16 * 16; }
+
+extern "C" int64_t mh_sgm_ws_bytes(int32_t B, int32_t H, int32_t W, int32_t D) {
+    if (B <= 0 || H <= 0 || W <= 0 || D <= 0) return 0;
+    const int64_t npix = (int64_t)B * H * W;
+    return sgm_align16(2 * npix * 8) + 4 * sgm_align16(npix * D) + sgm_align16(npix);
+}
+
+extern "C" int mh_sgm_proxy(const void* left, const void* right, int32_t frames_u8, void* ws, float* proxy, int32_t B, int32_t H, int32_t W, int32_t D,
+                            int32_t p1, int32_t p2, int32_t uniq, int32_t lr_tol, void* stream) {
+    MH_REQUIRE(left && right && ws && proxy, MH_ERR_ARG, "mh_sgm_proxy: null argument");
+    MH_REQUIRE(B > 0 && H > 0 && W > 0, MH_ERR_ARG, "mh_sgm_proxy: bad dimension");
+    MH_REQUIRE(H >= 7 && W >= 9, MH_ERR_ARG, "mh_sgm_proxy: the frame must hold one census window (H >= 7, W >= 9)");
+    MH_REQUIRE(D >= 1 && D <= 192 && D % 64 == 0, MH_ERR_UNSUPPORTED, "mh_sgm_proxy: D must be 64, 128 or 192");
+    MH_REQUIRE(p1 > 0 && p1 <= p2, MH_ERR_ARG, "mh_sgm_proxy: penalties must satisfy 0 < p1 <= p2");
+    MH_REQUIRE(64 + p2 <= 255, MH_ERR_ARG, "mh_sgm_proxy: 64 + p2 must fit 8 bits (the path volumes are uint8)");
+    MH_REQUIRE(uniq > 0 && uniq <= 100, MH_ERR_ARG, "mh_sgm_proxy: uniq must lie in 1 .. 100");
+    MH_REQUIRE(lr_tol >= 0, MH_ERR_ARG, "mh_sgm_proxy: lr_tol must not be negative");
+    MH_REQUIRE(mh_aligned16(ws), MH_ERR_ALIGN, "mh_sgm_proxy: ws must be 16-byte aligned");
+    MH_REQUIRE((int64_t)B * H * W < (1ll << 31) - 256 && B < 32768 && H < 65536 * SGM_CT_H, MH_ERR_UNSUPPORTED, "mh_sgm_proxy: too many pixels or frames");
+    SgmArgs a{};
+    const int64_t npix = (int64_t)B * H * W;
+    a.left = left; a.right = right;
+    a.census = (unsigned long long*)ws;
+    a.vol = (unsigned char*)ws + sgm_align16(2 * npix * 8);
+    a.vstride = sgm_align16(npix * D);
+    a.dr = a.vol + 4 * a.vstride;
+    a.out = proxy;
+    a.B = B; a.H = H; a.W = W; a.D = D; a.u8 = frames_u8 ? 1 : 0; a.p1 = p1; a.p2 = p2; a.uniq = uniq; a.lr_tol = lr_tol; a.npix = (int)npix;
+    hipStream_t s = (hipStream_t)stream;
+    hipLaunchKernelGGL(sgm_census_kernel, dim3((unsigned)mh_cdiv(W, SGM_CT_W), (unsigned)mh_cdiv(H, SGM_CT_H), (unsigned)(2 * B)), dim3(256), 0, s, a);
+    if (int e = mh_check_launch("sgm_census")) return e;
+    const dim3 lines((unsigned)(2 * H + 2 * W), (unsigned)B), pixels((unsigned)mh_cdiv(npix, 4));
+    switch (D / 64) {
+        case 1: hipLaunchKernelGGL(sgm_paths_kernel<1>, lines, dim3(64), 0, s, a); break;
+        case 2: hipLaunchKernelGGL(sgm_paths_kernel<2>, lines, dim3(64), 0, s, a); break;
+        default: hipLaunchKernelGGL(sgm_paths_kernel<3>, lines, dim3(64), 0, s, a); break;
+    }
+    if (int e = mh_check_launch("sgm_paths")) return e;
+    hipLaunchKernelGGL(sgm_right_kernel, dim3((unsigned)mh_cdiv(npix, 256)), dim3(256), 0, s, a);
+    if (int e = mh_check_launch("sgm_right")) return e;
+    switch (D / 64) {
+        case 1: hipLaunchKernelGGL(sgm_select_kernel<1>, pixels, dim3(256), 0, s, a); break;
+        case 2: hipLaunchKernelGGL(sgm_select_kernel<2>, pixels, dim3(256), 0, s, a); break;
+        default: hipLaunchKernelGGL(sgm_select_kernel<3>, pixels, dim3(256), 0, s, a); break;
+    }
+    mh_note_kernel("sgm_paths_kernel<%d> grid %d x %d, 4 launches", D / 64, 2 * H + 2 * W, B);
+    return mh_check_launch("sgm_select");
+}
+
 extern "C" int mh_resize_image_fwd(const float* in, float* out, int32_t B, int32_t Hi, int32_t Wi, int32_t C, int32_t Ho, int32_t Wo,
                                    void* stream) {
     MH_REQUIRE(in && out && B > 0 && Hi > 0 && Wi > 0 && C > 0 && Ho > 0 && Wo > 0, MH_ERR_ARG, "mh_resize_image_fwd: bad argument");

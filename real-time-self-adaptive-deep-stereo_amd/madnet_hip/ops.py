@@ -820,6 +820,21 @@ def proxy_loss(lib, pred, proxy, ws, result, dpred=None, weight=0.01, grad_scale
     lib.proxy_loss(_p(pred), _p(proxy), _p(ws), _p(result), _p(dpred), weight, grad_scale, B, H, W, _p(stream))
 
 
+def sgm_proxy_ws(lib, B, H, W, D, device):
+    """the workspace of sgm_proxy (census words, four path volumes, the right view's winners): torch allocations are at least 16-byte aligned"""
+    return torch.empty(int(lib.sgm_ws_bytes(B, H, W, D)), dtype=torch.uint8, device=device)
+
+
+def sgm_proxy(lib, left, right, ws, out, max_disp=128, p1=10, p2=120, uniq=95, lr_tol=1, stream=None):
+    """left, right [B,H,W,3] uint8 or float32 (0..255) -> out [B,H,W] float32 proxy disparities, 0 = rejected (mh_sgm_proxy).  Called directly, never recorded."""
+    B, H, W, c = left.shape
+    assert c == 3 and right.shape == left.shape and right.dtype == left.dtype and left.dtype in (torch.uint8, torch.float32), "sgm_proxy: [B,H,W,3] uint8 or float32"
+    assert left.is_contiguous() and right.is_contiguous() and out.is_contiguous() and out.dtype == torch.float32 and out.numel() == B * H * W
+    assert ws.numel() * ws.element_size() >= lib.sgm_ws_bytes(B, H, W, int(max_disp)), "sgm_proxy: workspace too small"
+    lib.sgm_proxy(_p(left), _p(right), int(left.dtype == torch.uint8), _p(ws), _p(out), B, H, W, int(max_disp), int(p1), int(p2), int(uniq), int(lr_tol), _p(stream))
+    return out
+
+
 def proxy_loss_scaled(lib, pred, proxy, ws, result, scale, dpred=None, weight=0.1, grad_scale=1.0, stream=None):
     """proxy_loss of the prediction and the proxy labels both resized to (H // scale, W // scale), the labels divided by scale (a MAD block's loss under
     --reprojectionScale, Stereo_Continual_Adaptation.py:95-112) in one op; dpred = its gradient on the full-size grid (optional).  ws: proxy_scaled_ws_floats."""
