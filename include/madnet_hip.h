@@ -487,8 +487,10 @@ int mh_conv_image_ok(int32_t C, int32_t N, int32_t kh, int32_t kw, int32_t strid
 
 /* ---- loss_factory.get_reprojection_loss('mean_SSIM_l1') forward + gradient w.r.t. the
  *      disparity (Losses/loss_factory.py:128-164,353-395; preprocessing.py:121-230) ------
- * left,right: [B,H,W,3] in 0..255;  disp: [B,H,W].  ws: workspace of mh_loss_ws_floats()
- * floats.  result[0] = loss, result[1] = mean SSIM term, result[2] = mean L1 term.
+ * left,right: [B,H,W,3] in 0..255;  disp: [B,H,W], any H, W >= 3.  ws: 16-byte aligned workspace of at least
+ * mh_loss_ws_floats(B, H, W) floats -- for every accepted shape no call reads or writes behind that many, and nothing
+ * in it needs initialising (every partial sum is written by its own workgroup before the final reduction reads it).
+ * result[0] = loss, result[1] = mean SSIM term, result[2] = mean L1 term.
  * ddisp (may be NULL: forward only) = grad_scale * dLoss/ddisp. */
 int64_t mh_loss_ws_floats(int32_t B, int32_t H, int32_t W);
 int mh_reprojection_loss(const float* left, const float* right, const float* disp,

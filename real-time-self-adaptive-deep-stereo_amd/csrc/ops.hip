@@ -1746,9 +1746,13 @@ extern "C" int mh_pad_reflect(const float* in, float* out, int32_t B, int32_t H,
 
 static inline int64_t nblk(int64_t n) { return (n + 255) / 256; }
 
+// workgroups of loss_tile_kernel = partial sums per array: one LT_H x LT_W tile each, edge tiles included however few pixels they hold
+static inline int64_t loss_tiles(int32_t B, int32_t H, int32_t W) { return (int64_t)B * mh_cdiv(W, LT_W) * mh_cdiv(H, LT_H); }
+
+// [ maps: 8 n + 12 nw floats, unused since the tile kernel | L1 partial sums: one per tile | SSIM partial sums: one per tile ]
 extern "C" int64_t mh_loss_ws_floats(int32_t B, int32_t H, int32_t W) {
     const int64_t n = (int64_t)B * H * W, nw = (int64_t)B * (H - 2) * (W - 2);
-    return 8 * n + 12 * nw + nblk(n) + nblk(nw) + 64;
+    return 8 * n + 12 * nw + 2 * loss_tiles(B, H, W);
 }
 
 extern "C" int mh_reprojection_loss(const float* left, const float* right, const float* disp, float* ws, float* result,
@@ -1767,12 +1771,12 @@ extern "C" int mh_reprojection_loss_phase(const float* left, const float* right,
     LossArgs a{};
     a.left = left; a.right = right; a.disp = disp; a.result = result; a.ddisp = ddisp; a.grad_scale = grad_scale;
     a.B = B; a.H = H; a.W = W;
-    const int tiles_x = (W + LT_W - 1) / LT_W, tiles_y = (H + LT_H - 1) / LT_H;
-    const int64_t ntiles = (int64_t)B * tiles_x * tiles_y;               // <= nblk(n): the workspace keeps its layout
+    const int tiles_x = mh_cdiv(W, LT_W), tiles_y = mh_cdiv(H, LT_H);
+    const int64_t ntiles = loss_tiles(B, H, W);                           // the count mh_loss_ws_floats sizes the two partial arrays with
     MH_REQUIRE(ntiles < (1ll << 31), MH_ERR_ARG, "mh_reprojection_loss: too many tiles");
     a.rep = ws; a.drep = ws + 4 * n; a.coef = ws + 8 * n;                  // (maps: LDS only since the tile kernel; the offsets keep the layout)
     a.part1 = ws + 8 * n + 12 * nw; a.nblk1 = (int)ntiles;
-    a.part2 = a.part1 + nblk(n); a.nblk2 = (int)ntiles;
+    a.part2 = a.part1 + ntiles; a.nblk2 = (int)ntiles;
     hipStream_t s = (hipStream_t)stream;
     if (phase != 2) hipLaunchKernelGGL(loss_tile_kernel, dim3((unsigned)ntiles), dim3(256), 0, s, a, tiles_x, tiles_y, ddisp ? 1 : 0);
     if (phase != 1) hipLaunchKernelGGL(loss_final_kernel, dim3(1), dim3(256), 0, s, a);

@@ -213,12 +213,18 @@ def test_reprojection_loss_and_grad(backend, shape):
     dc = disp.cpu().requires_grad_(True)
     ref = T.reprojection_loss(dc[..., None], left.cpu(), right.cpu())
     (gd_ref,) = torch.autograd.grad(ref, [dc])
+    d64 = disp.cpu().double().requires_grad_(True)
+    (g64,) = torch.autograd.grad(T.reprojection_loss(d64[..., None], left.cpu(), right.cpu()), [d64])
+    e32 = (gd_ref.double() - g64).abs().max().item()                 # what float32 arithmetic of this length costs the oracle itself
     ws = torch.zeros(backend.lib.loss_ws_floats(B, H, W), device=dev)
     res = torch.zeros(4, device=dev); dd = torch.full((B, H, W), float("nan"), device=dev)
     ops.reprojection_loss(backend.lib, left, right, disp, ws, res, dd, grad_scale=1.0)
     backend.sync()
     assert abs(res[0].item() - ref.item()) <= 2e-6 * max(1.0, abs(ref.item()))
-    ok, err = _close(dd, gd_ref, rtol=2e-4, atol=1e-7); assert ok, err
+    # per pixel against the float64 oracle: the same float32 arithmetic in another order, three bits of headroom (tests/test_loss_tiles.py)
+    assert torch.isfinite(dd).all()
+    err = (dd.cpu().double() - g64).abs().max().item()
+    assert err <= 8 * e32 + 1e-12, (err, e32)
 
 
 def test_reprojection_loss_smooth_images(backend):
