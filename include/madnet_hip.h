@@ -76,6 +76,12 @@ typedef struct mh_conv_desc {
                                           Tensors stay fp32 in memory in every mode */
 } mh_conv_desc;
 
+/* Store contract (tests/test_conv_footprint.py): a launch writes channels [0, N) of every output pixel's row and nothing else -- `out` may be a
+ * channel slice of a wider row (out_ld > N, any alignment: slices that are not 16-byte aligned take the element-wise epilogues) whose other
+ * channels belong to somebody else.  ONE exception, the padded rows of an input gradient (ConvArgs::vecCpad): mode 1, N not a multiple of 4,
+ * no bias, out (and mask_ref) 16-byte aligned with out_ld (mask_ld) a multiple of 4 and >= N rounded up to 4 -- the patch-staged bf16 kernel
+ * then stores whole 16-byte groups and the channels N .. round_up(N, 4) - 1 receive zeros (with d->accumulate: what they held, times the mask
+ * factor); an out_shadow's same channels likewise.  Give such a slice its row padding, never a neighbour's channels, behind channel N - 1. */
 int mh_conv2d(const mh_conv_desc* d, const float* in, const float* w, const float* bias,
               float* out, const float* mask_ref, void* stream);
 
@@ -89,8 +95,8 @@ int mh_conv2d(const mh_conv_desc* d, const float* in, const float* w, const floa
  * (the engines do it once per step, one launch for every layer).  Same arithmetic as the LDS-staged split-bf16 kernel. */
 int mh_conv2d_wb(const mh_conv_desc* d, const float* in, const float* w, const void* wb, const float* bias,
                  float* out, const float* mask_ref, void* stream);
-/* mh_conv2d_wb that ALSO writes out_shadow = bf16(out) as [pixel][N rounded up to 32] (round to nearest even; the padding channels are not
- * touched: allocate the shadow zeroed) -- the operand layout of mh_wgrad_stream, produced where the value is computed instead of by a
+/* mh_conv2d_wb that ALSO writes out_shadow = bf16(out) as [pixel][N rounded up to 32] (round to nearest even, bit for bit the rounding of the
+ * stored fp32 value; the padding channels [N, round_up(N, 32)) are not touched -- they keep whatever they held: allocate the shadow zeroed) -- the operand layout of mh_wgrad_stream, produced where the value is computed instead of by a
  * cast pass (+2 bytes per element written, nothing re-read).  wb and out_shadow may be NULL (then exactly mh_conv2d_wb / mh_conv2d). */
 int mh_conv2d_sh(const mh_conv_desc* d, const float* in, const float* w, const void* wb, const float* bias,
                  float* out, const float* mask_ref, void* out_shadow, void* stream);
@@ -431,7 +437,8 @@ int mh_conv2d_sh2(const mh_conv_desc* d, const float* in, const void* in_shadow,
 /* mh_conv2d_sh2 with two more options of the patch-staged input-gradient kernel (every other kernel ignores them and behaves like mh_conv2d_sh2):
  * mask_shadow = the bf16 shadow of mask_ref (pixel stride = N rounded up to 32): the leaky mask tests only the sign, so 8 bytes of the shadow
  * replace 16 of the fp32 activation; flags & MH_CONV_SHADOW_ONLY: the fp32 result is NOT stored, only out_shadow (legal when every consumer of
- * the result takes its shadow -- ask mh_conv2d_takes_shadows for the consuming launch; needs out_shadow, no accumulation).
+ * the result takes its shadow -- ask mh_conv2d_takes_shadows for the consuming launch; needs out_shadow, no accumulation; not one byte of `out` is
+ * written then, the shadow holds the bits it holds without the flag).
  * mh_conv2d_takes_shadows(d, ...) != 0 if the launch described by d / these pointers would stage in_shadow (and honour the options), else 0. */
 #define MH_CONV_SHADOW_ONLY 1
 /* flags & MH_CONV_IN_F32_STALE / MH_CONV_MASK_F32_STALE: the caller did not store the fp32 `in` / `mask_ref` (its producer ran with
@@ -443,7 +450,8 @@ int mh_conv2d_sh2(const mh_conv_desc* d, const float* in, const void* in_shadow,
 int mh_conv2d_sh3(const mh_conv_desc* d, const float* in, const void* in_shadow, const float* w, const void* wb, const float* bias,
                   float* out, const float* mask_ref, const void* mask_shadow, void* out_shadow, int32_t flags, void* stream);
 int mh_conv2d_takes_shadows(const mh_conv_desc* d, const float* in, const float* w, const void* wb, float* out, const float* mask_ref);
-/* mh_conv2d_sh that writes BOTH planes of its result, out_hi = bf16(out) and out_lo = bf16(out - out_hi) ([pixel][N rounded up to 32]): the producer side
+/* mh_conv2d_sh that writes BOTH planes of its result, out_hi = bf16(out) and out_lo = bf16(out - out_hi) ([pixel][N rounded up to 32], padding channels
+ * not touched, as for mh_conv2d_sh): the producer side
  * of mh_conv2d_planes for layers that run from fp32 operands (the exact-fp32 stride-2 pyramid layers in front of conv4 / conv6).  The tiled kernel's
  * vector epilogue stores them itself; behind any other kernel family one split launch follows. */
 int mh_conv2d_sh4(const mh_conv_desc* d, const float* in, const float* w, const void* wb, const float* bias, float* out, const float* mask_ref,

@@ -1299,9 +1299,12 @@ static int conv_entry(const mh_conv_desc* d, const float* in, const float* w, co
         a.in_bytes = (unsigned)inb; a.w_bytes = (unsigned)wb;
         const int64_t ob = (((int64_t)d->B * d->Ho * d->Wo - 1) * d->out_ld + d->N) * 4;
         const int64_t mb = mask_ref ? (((int64_t)d->B * d->Ho * d->Wo - 1) * d->mask_ld + d->N) * 4 : 0;
+        const bool fits = ob < (1ll << 31) - 64 && mb < (1ll << 31) - 64;
         a.vecC = (d->N % 4 == 0) && (d->out_ld % 4 == 0) && mh_aligned16(out) && (!bias || mh_aligned16(bias)) &&
-                 (!mask_ref || (d->mask_ld % 4 == 0 && mh_aligned16(mask_ref))) && ob < (1ll << 31) - 64 && mb < (1ll << 31) - 64;
-        a.out_bytes = (unsigned)(a.vecC ? ob : 0); a.mask_bytes = (unsigned)(a.vecC ? mb : 0);
+                 (!mask_ref || (d->mask_ld % 4 == 0 && mh_aligned16(mask_ref))) && fits;
+        // the ranges of the bounds-checked epilogue loads do NOT depend on vecC: the small-layer bank kernel stores element by element (any alignment) and
+        // reads the old output / the mask through them -- with zero bytes for an unaligned slice it dropped the accumulation and masked every element
+        a.out_bytes = (unsigned)(fits ? ob : 0); a.mask_bytes = (unsigned)(fits ? mb : 0);
         // (the estimators' first layers: 38 / 70 / ... input channels in rows of 40 / 72 / ...: see ConvArgs::vecCpad)
         a.vecCpad = 0;
         const int n4 = (d->N + 3) / 4 * 4;

@@ -1239,6 +1239,7 @@ bool mh_conv_bank_small_ok(const ConvArgs& a) {
     // there, profiles/r03_experiments.txt #11; in the forward pass that level runs split-bf16 on the big bank kernel)
     const int maxpix = a.mode == 1 ? 2 * bank_small_maxpix() : bank_small_maxpix();
     if (!a.wb || !(a.bf16 || a.x3) || (a.x3 && a.mode != 0)) return false;
+    if ((a.accumulate && !a.out_bytes) || (a.mask_ref && !a.mask_bytes)) return false;      // (>= 2 GiB rows: the epilogue operands are range-checked 32-bit loads)
     const bool s1 = a.stride == 1 && a.pad_t == a.dil && a.pad_l == a.dil && a.Hi == a.Ho && a.Wi == a.Wo;
     const bool s2 = a.stride == 2 && a.mode == 0 && a.dil == 1 && a.pad_t >= 0 && a.pad_t <= 1 && a.pad_l >= 0 && a.pad_l <= 1 &&
                     a.Ho == (a.Hi + 1) / 2 && a.Wo == (a.Wi + 1) / 2;

@@ -1281,6 +1281,7 @@ static __global__ __launch_bounds__(256) void plane_split_one_kernel(mh_plane_se
     if (item >= sg.npix * g8) return;
     const int64_t pix = item / g8;
     const int c0 = (int)(item - pix * g8) * 8;
+    if (c0 >= sg.C) return;                    // (the planes' padding channels are not touched: mh_conv2d_sh4's contract, unlike mh_plane_split's zero fill)
     const float* s = sg.src + pix * sg.src_ld + c0;
     float v[8];
 #pragma unroll
@@ -1288,8 +1289,19 @@ static __global__ __launch_bounds__(256) void plane_split_one_kernel(mh_plane_se
     unsigned hh[4], ll[4];
 #pragma unroll
     for (int e = 0; e < 4; ++e) mh_split_bf16x2(v[2 * e], v[2 * e + 1], hh[e], ll[e]);
-    *reinterpret_cast<u32x4*>(reinterpret_cast<unsigned short*>(sg.hi) + pix * sg.dst_ld + c0) = (u32x4){hh[0], hh[1], hh[2], hh[3]};
-    if (sg.lo) *reinterpret_cast<u32x4*>(reinterpret_cast<unsigned short*>(sg.lo) + pix * sg.dst_ld + c0) = (u32x4){ll[0], ll[1], ll[2], ll[3]};
+    unsigned short* const hi = reinterpret_cast<unsigned short*>(sg.hi) + pix * sg.dst_ld + c0;
+    unsigned short* const lo = sg.lo ? reinterpret_cast<unsigned short*>(sg.lo) + pix * sg.dst_ld + c0 : nullptr;
+    if (c0 + 8 <= sg.C) {
+        *reinterpret_cast<u32x4*>(hi) = (u32x4){hh[0], hh[1], hh[2], hh[3]};
+        if (lo) *reinterpret_cast<u32x4*>(lo) = (u32x4){ll[0], ll[1], ll[2], ll[3]};
+    } else {
+#pragma unroll
+        for (int e = 0; e < 8; ++e)
+            if (c0 + e < sg.C) {
+                hi[e] = (unsigned short)(hh[e >> 1] >> (16 * (e & 1)));
+                if (lo) lo[e] = (unsigned short)(ll[e >> 1] >> (16 * (e & 1)));
+            }
+    }
 }
 // one tensor, arguments by value (the fallback of mh_conv2d_sh4 for kernel families whose epilogue does not write the lo plane)
 int mh_plane_split_one(const float* src, int src_ld, int C, void* hi, void* lo, int dst_ld, int64_t npix, hipStream_t s) {

@@ -56,19 +56,29 @@ __global__ __launch_bounds__(256) void shadow_cast_kernel(const mh_shadow_seg* _
     *reinterpret_cast<u32x4*>(reinterpret_cast<unsigned short*>(sg.dst) + pix * sg.dst_ld + c0) = o;
 }
 
+// the cast behind a conv kernel whose epilogue has no shadow store (mh_conv2d_sh): unlike mh_shadow_cast it leaves the padding channels [C, dst_ld) alone,
+// as the epilogues that store the shadow themselves do (include/madnet_hip.h: "the padding channels are not touched")
 __global__ __launch_bounds__(256) void shadow_cast_one_kernel(mh_shadow_seg sg) {
     const int g8 = sg.dst_ld >> 3;
     const int64_t item = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (item >= sg.npix * g8) return;
     const int64_t pix = item / g8;
     const int c0 = (int)(item - pix * g8) * 8;
+    if (c0 >= sg.C) return;
     const float* s = sg.src + pix * sg.src_ld + c0;
+    unsigned short* const dst = reinterpret_cast<unsigned short*>(sg.dst) + pix * sg.dst_ld + c0;
     float v[8];
 #pragma unroll
     for (int e = 0; e < 8; ++e) v[e] = (c0 + e < sg.C) ? s[e] : 0.f;
-    u32x4 o;
-    o[0] = mh_pack_bf16(v[0], v[1]); o[1] = mh_pack_bf16(v[2], v[3]); o[2] = mh_pack_bf16(v[4], v[5]); o[3] = mh_pack_bf16(v[6], v[7]);
-    *reinterpret_cast<u32x4*>(reinterpret_cast<unsigned short*>(sg.dst) + pix * sg.dst_ld + c0) = o;
+    if (c0 + 8 <= sg.C) {
+        u32x4 o;
+        o[0] = mh_pack_bf16(v[0], v[1]); o[1] = mh_pack_bf16(v[2], v[3]); o[2] = mh_pack_bf16(v[4], v[5]); o[3] = mh_pack_bf16(v[6], v[7]);
+        *reinterpret_cast<u32x4*>(dst) = o;
+    } else {
+#pragma unroll
+        for (int e = 0; e < 8; ++e)
+            if (c0 + e < sg.C) dst[e] = (unsigned short)mh_pack_bf16(v[e], 0.f);
+    }
 }
 
 // ---- the streaming kernel ---------------------------------------------------------------------------------------------------------------

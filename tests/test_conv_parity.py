@@ -371,8 +371,7 @@ PATCH_CASES = [(1, 12, 20, 128, 128, 1, 128), (1, 9, 21, 96, 64, 2, 64), (2, 10,
                (1, 12, 19, 96, 128, 1, 128 + 256), (1, 9, 17, 128, 64, 1, 128 + 256 + 2048)]
 
 
-# K = 32 (one chunk per tap, five weight tiles with a dead last half) in both directions.  Added after the round's GPU budget
-# was spent: run on the emulator only (the same instances run on the MI355X inside the engine / bench: the 64->32 layer's dgrad)
+# K = 32 (one chunk per tap, five weight tiles with a dead last half) in both directions
 PATCH_CASES_K32 = [(1, 9, 17, 64, 32, 1, 128 + 256), (1, 9, 17, 32, 64, 1, 128 + 256), (1, 9, 18, 32, 48, 2, 64),
                    (1, 9, 17, 64, 160, 1, 128 + 256)]      # + Cout = 160: two column tiles, the second one partly dead (no such layer in either net)
 # 32-column tile (round 3): the layers with <= 32 output columns -- 32 -> 32, 64 -> 32 and their input gradients
@@ -385,8 +384,6 @@ def test_conv_bf16_patch_kernel(backend, case):
     input gradient with accumulate + leaky-grad mask, against the oracle on bf16-rounded operands; every pixel tile
     (64 / 128 pixels, 8-wave variant), dilation sub-lattices with ragged edges, Cin = 38 (row padding must not leak)."""
     B, H, W, Ci, Co, dil, mode = case
-    if case in PATCH_CASES_K32 and backend.name != "emul":
-        pytest.skip("emulator-only case (see PATCH_CASES_K32)")
     dev = backend.device
     x = _rand((B, H, W, Ci), 91, dev)
     w = _rand((3, 3, Ci, Co), 92, dev, 0.2)
