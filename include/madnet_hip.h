@@ -425,6 +425,25 @@ int mh_frame_prepare(const mh_frame_seg* segs, int32_t B, int32_t H, int32_t W,
 int64_t mh_sgm_ws_bytes(int32_t B, int32_t H, int32_t W, int32_t D);
 int mh_sgm_proxy(const void* left, const void* right, int32_t frames_u8, void* ws, float* proxy,
                  int32_t B, int32_t H, int32_t W, int32_t D, int32_t p1, int32_t p2, int32_t uniq, int32_t lr_tol, void* stream);
+/* mh_sgm_proxy with two options (additive: the ABI version stays); mh_sgm_proxy(...) is mh_sgm_proxy_ex(..., 4, 0, stream) and mh_sgm_ws_bytes(...) is
+ * mh_sgm_ws_bytes_ex(..., 4, 0): the same bits, the same bytes.  Any other value of `paths` or `median` is MH_ERR_ARG, nothing launched.
+ *   paths = 8: the four diagonal paths are aggregated as well, paths 4 .. 7 with steps (dy, dx) = (+1,+1), (+1,-1), (-1,+1), (-1,-1).  A diagonal line starts at every
+ *      pixel whose predecessor (y - dy, x - dx) lies outside the frame (H + W - 1 lines per direction); at its first pixel L = C, every later pixel takes the
+ *      recurrence of the axis paths.  L <= 64 + p2 <= 255 in every direction, S = the sum of all eight volumes <= 2040; winner, uniqueness, the right view's
+ *      winner, the left-right check and the parabola are the definitions above applied to that S.  On frames only a few dozen rows high a diagonal line is too
+ *      short to settle and eight paths give WORSE labels than four: the option is meant for frames of the workload's size.
+ *   median = 1: a 3 x 3 median of the finished label map, after rejection.  A rejected pixel (0) stays 0; a valid pixel becomes the lower median of the valid
+ *      (> 0) labels among those of its 3 x 3 neighbours that lie inside its own frame (no replicate border, nothing from the next image of a batch): with the
+ *      n >= 1 valid values in ascending order, the one at index (n - 1) / 2.  A copy of one input value, nothing is averaged.
+ * ws: mh_sgm_ws_bytes_ex bytes, 16-byte aligned, each part rounded up to 16 bytes: census words [2][B][H][W] (8 bytes) | `paths` uint8 volumes [B][H][W][D], path
+ * 0 first | paths = 8 only: their sum S [B][H][W][D] (uint16), folded once for the right-view and select passes | the right view's winners [B][H][W] (uint8) |
+ * median = 1 only: the labels before the filter [B][H][W] (float32).  mh_sgm_ws_bytes_ex is 0 for a
+ * non-positive dimension or an illegal option.  As for mh_sgm_proxy: integer arithmetic up to the sub-pixel step, no atomics, every element of `proxy` written,
+ * two calls give the same bits.  Four launches, one more for eight paths, one more with the median; never part of a plan. */
+int64_t mh_sgm_ws_bytes_ex(int32_t B, int32_t H, int32_t W, int32_t D, int32_t paths, int32_t median);
+int mh_sgm_proxy_ex(const void* left, const void* right, int32_t frames_u8, void* ws, float* proxy,
+                    int32_t B, int32_t H, int32_t W, int32_t D, int32_t p1, int32_t p2, int32_t uniq, int32_t lr_tol,
+                    int32_t paths, int32_t median, void* stream);
 
 /* ---- preprocessing.pad_image (REFLECT, preprocessing.py:7-29) fused with the float cast
  *      and the channel padding 3 -> out_ld (extra channels zero) ------------------------ */

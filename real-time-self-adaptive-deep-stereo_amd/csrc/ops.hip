@@ -1420,18 +1420,22 @@ extern "C" int mh_frame_prepare(const mh_frame_seg* segs, int32_t B, int32_t H, 
     return mh_check_launch("frame_apply");
 }
 
-// ---- proxy labels of the continual loop on the device (mh_sgm_proxy): census + four-path semi-global matching ---------------------------------------------------
+// ---- proxy labels of the continual loop on the device (mh_sgm_proxy, mh_sgm_proxy_ex): census + four- or eight-path semi-global matching, 3x3 median --------------
 // Replaces the proxy column of the continual list (an external matcher's PNGs).  Integer arithmetic up to the sub-pixel step, no atomics, every launch writes
 // what the next one reads: the result does not depend on launch shape or order.  Workspace: census words [2][B][H][W] (8 bytes), one uint8 volume [B][H][W][D]
 // per path (L_r <= 64 + p2 <= 255), the right view's winner [B][H][W] (uint8).  The matching cost is never stored: a path step recomputes
 // popcount(cL(y, x) ^ cR(y, x - d)) from the census rows (16 bytes per pixel and view instead of a D-byte volume read by four paths).
+// mh_sgm_proxy_ex: P = 4 or 8 volumes (the four diagonals behind the four axis paths; the kernels are templated on P); for P = 8 one more pass folds the eight
+// volumes into their sum S, uint16 [B][H][W][D] behind the volumes, which the right-view and select kernels read instead (the right-view walk gathers single
+// elements, and gathered from eight volumes it took 7.26 ms at 375 x 1242, D = 128, against 1.05 ms from four: profiles/sgm_proxy.txt); with the median the
+// labels before the filter, float [B][H][W], lie behind the right view's winners.
 #define SGM_BIG (1 << 20)
 #define SGM_CT_W 32             // census tile: 32 x 8 pixels per workgroup, halo 4 x 3
 #define SGM_CT_H 8
 
 struct SgmArgs {
     const void* left; const void* right;
-    unsigned long long* census; unsigned char* vol; unsigned char* dr; float* out;
+    unsigned long long* census; unsigned char* vol; unsigned short* fold; unsigned char* dr; float* out;      // fold: P = 8 only; out: what sgm_select_kernel writes (proxy, or the map in front of the median)
     int64_t vstride;            // bytes between two path volumes
     int B, H, W, D, u8, p1, p2, uniq, lr_tol, npix;
 };
@@ -1497,15 +1501,26 @@ __device__ __forceinline__ void sgm_cost(const unsigned long long* __restrict__ 
     }
 }
 
-// Aggregation, all four paths in one launch: grid (2 H + 2 W, B), one wave per path line -- a row left->right / right->left, a column top->bottom /
-// bottom->top --, K = D / 64 neighbouring disparities per lane: d -/+ 1 come from the neighbouring lane, m from a wave min.  Sequential along the line (the
+// Aggregation, all P paths in one launch: grid (2 H + 2 W [+ 4 (H + W - 1)], B), one wave per path line -- a row left->right / right->left, a column top->bottom /
+// bottom->top, and for P = 8 the diagonals (dy, dx) = (+1,+1), (+1,-1), (-1,+1), (-1,-1): a line starts at every pixel whose predecessor lies outside the frame
+// (line j < W at column j of the first row in walking order, the others at the rows behind it on the side the walk comes from) and runs until it leaves the
+// frame --, K = D / 64 neighbouring disparities per lane: d -/+ 1 come from the neighbouring lane, m from a wave min.  Sequential along the line (the
 // step's chain is two shuffles + the six of the reduction), parallel across lines and paths; the next pixel's costs are fetched before the step.
-template <int K>
+template <int K, int P>
 __global__ __launch_bounds__(64) void sgm_paths_kernel(SgmArgs a) {
     const int lane = threadIdx.x, b = blockIdx.y;
     int line = blockIdx.x, path, y, x, dy = 0, dx = 0, n;
     if (line < 2 * a.H) { path = line & 1; y = line >> 1; x = path ? a.W - 1 : 0; dx = path ? -1 : 1; n = a.W; }
-    else { line -= 2 * a.H; path = 2 + (line & 1); x = line >> 1; y = (line & 1) ? a.H - 1 : 0; dy = (line & 1) ? -1 : 1; n = a.H; }
+    else if (P == 4 || line < 2 * a.H + 2 * a.W) { line -= 2 * a.H; path = 2 + (line & 1); x = line >> 1; y = (line & 1) ? a.H - 1 : 0; dy = (line & 1) ? -1 : 1; n = a.H; }
+    else {
+        line -= 2 * a.H + 2 * a.W;
+        const int per = a.H + a.W - 1, dir = line / per, j = line - dir * per, t = j - a.W + 1;      // t >= 1: the line starts in row t of the walk, at the side
+        path = 4 + dir; dy = (dir & 2) ? -1 : 1; dx = (dir & 1) ? -1 : 1;
+        const int row = t > 0 ? t : 0;
+        y = dy > 0 ? row : a.H - 1 - row;
+        x = t > 0 ? (dx > 0 ? 0 : a.W - 1) : j;
+        n = min(dy > 0 ? a.H - y : y + 1, dx > 0 ? a.W - x : x + 1);
+    }
     const int64_t frame = (int64_t)b * a.H * a.W;
     const unsigned long long* __restrict__ cl = a.census + frame;
     const unsigned long long* __restrict__ cr = a.census + a.npix + frame;
@@ -1551,30 +1566,52 @@ __global__ __launch_bounds__(64) void sgm_paths_kernel(SgmArgs a) {
 // S(pixel, d) = the sum of the four paths; p points at path 0's byte
 __device__ __forceinline__ int sgm_sum4(const unsigned char* __restrict__ p, int64_t vs) { return (int)p[0] + (int)p[vs] + (int)p[2 * vs] + (int)p[3 * vs]; }
 
+// P = 8: S = the sum of the eight volumes, once, as uint16 (S <= 2040).  One thread per 8 neighbouring elements: eight 8-byte loads, one 16-byte store
+__global__ __launch_bounds__(256) void sgm_fold_kernel(SgmArgs a, int64_t n8) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + (int64_t)threadIdx.x;
+    if (i >= n8) return;
+    int s[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+#pragma unroll
+    for (int p = 0; p < 8; ++p) {
+        const unsigned long long w = *reinterpret_cast<const unsigned long long*>(a.vol + p * a.vstride + i * 8);
+#pragma unroll
+        for (int k = 0; k < 8; ++k) s[k] += (int)((w >> (8 * k)) & 255u);
+    }
+    unsigned long long o[2];
+#pragma unroll
+    for (int h = 0; h < 2; ++h)
+        o[h] = (unsigned long long)s[4 * h] | ((unsigned long long)s[4 * h + 1] << 16) | ((unsigned long long)s[4 * h + 2] << 32) | ((unsigned long long)s[4 * h + 3] << 48);
+    unsigned long long* q = reinterpret_cast<unsigned long long*>(a.fold + i * 8);
+    q[0] = o[0]; q[1] = o[1];
+}
+
 // the right view's winner from the same volume: dR(y, x') = argmin over d with x' + d < W of S(y, x' + d, d), lowest d on ties.  One lane per pixel walks the diagonal
+template <int P>
 __global__ __launch_bounds__(256) void sgm_right_kernel(SgmArgs a) {
     const int pix = (int)blockIdx.x * 256 + (int)threadIdx.x;
     if (pix >= a.npix) return;
     const int x = pix % a.W, nd = min(a.D, a.W - x);
     const unsigned char* __restrict__ p = a.vol + (int64_t)pix * a.D;
+    const unsigned short* __restrict__ f = a.fold + (int64_t)pix * a.D;
     int best = SGM_BIG, bd = 0;
 #pragma unroll 4
     for (int d = 0; d < nd; ++d) {
-        const int s = sgm_sum4(p + (int64_t)d * (a.D + 1), a.vstride);
+        const int s = P == 8 ? (int)f[(int64_t)d * (a.D + 1)] : sgm_sum4(p + (int64_t)d * (a.D + 1), a.vstride);
         if (s < best) { best = s; bd = d; }
     }
     a.dr[pix] = (unsigned char)bd;
 }
 
 // winner, uniqueness, left-right check, sub-pixel: one wave per pixel (4 per workgroup), K disparities per lane.  Every pixel is written (0 = rejected)
-template <int K>
+template <int K, int P>
 __global__ __launch_bounds__(256) void sgm_select_kernel(SgmArgs a) {
     const int lane = threadIdx.x & 63, pix = (int)blockIdx.x * 4 + ((int)threadIdx.x >> 6);
     if (pix >= a.npix) return;                                          // wave-uniform
     const unsigned char* __restrict__ p = a.vol + (int64_t)pix * a.D + lane * K;
+    const unsigned short* __restrict__ f = a.fold + (int64_t)pix * a.D + lane * K;
     int S[K], key = 0x7fffffff;
 #pragma unroll
-    for (int k = 0; k < K; ++k) { S[k] = sgm_sum4(p + k, a.vstride); key = min(key, (S[k] << 8) | (lane * K + k)); }      // S <= 1020, d < 256: lowest d on ties
+    for (int k = 0; k < K; ++k) { S[k] = P == 8 ? (int)f[k] : sgm_sum4(p + k, a.vstride); key = min(key, (S[k] << 8) | (lane * K + k)); }      // S <= 255 P <= 2040, d < 256: lowest d on ties
     key = sgm_wave_min(key);
     const int d1 = key & 255, s1 = key >> 8;
     int s2 = SGM_BIG, sm = SGM_BIG, sp = SGM_BIG;
@@ -1599,54 +1636,119 @@ __global__ __launch_bounds__(256) void sgm_select_kernel(SgmArgs a) {
     a.out[pix] = ok ? o : 0.f;
 }
 
-static inline int64_t sgm_align16(int64_t n) { return (n + 15) / 16 * 16; }
-
-extern "C" int64_t mh_sgm_ws_bytes(int32_t B, int32_t H, int32_t W, int32_t D) {
-    if (B <= 0 || H <= 0 || W <= 0 || D <= 0) return 0;
-    const int64_t npix = (int64_t)B * H * W;
-    return sgm_align16(2 * npix * 8) + 4 * sgm_align16(npix * D) + sgm_align16(npix);
+// 3x3 median of the finished label map, one thread per pixel: a rejected pixel (0) stays 0, a valid one becomes the lower median -- index (n - 1) / 2 of the n valid
+// values in ascending order -- of the valid labels among its neighbours inside its own frame.  A copy of one input value.  No sorting network and no register
+// array indexed at run time: a label that is absent counts as +inf, every candidate counts the candidates that sort before it (ties by position), and the one
+// whose count is (n - 1) / 2 is kept; n >= 1 makes that one a valid label.
+__global__ __launch_bounds__(256) void sgm_median_kernel(const float* __restrict__ in, float* __restrict__ out, int H, int W, int npix) {
+    const int pix = (int)blockIdx.x * 256 + (int)threadIdx.x;
+    if (pix >= npix) return;
+    const int x = pix % W, y = (pix / W) % H;
+    float v[9];
+    int n = 0;
+#pragma unroll
+    for (int i = 0; i < 9; ++i) {
+        const int oy = i / 3 - 1, ox = i % 3 - 1;
+        const bool inside = y + oy >= 0 && y + oy < H && x + ox >= 0 && x + ox < W;
+        const float t = in[pix + (inside ? oy * W + ox : 0)];
+        const bool valid = inside && t > 0.f;
+        v[i] = valid ? t : __builtin_inff();
+        n += valid ? 1 : 0;
+    }
+    const int want = (n - 1) >> 1;
+    float r = 0.f;
+#pragma unroll
+    for (int i = 0; i < 9; ++i) {
+        int before = 0;
+#pragma unroll
+        for (int j = 0; j < 9; ++j)
+            if (j != i) before += (v[j] < v[i] || (v[j] == v[i] && j < i)) ? 1 : 0;
+        if (before == want) r = v[i];
+    }
+    out[pix] = v[4] < __builtin_inff() ? r : 0.f;
 }
 
-extern "C" int mh_sgm_proxy(const void* left, const void* right, int32_t frames_u8, void* ws, float* proxy, int32_t B, int32_t H, int32_t W, int32_t D,
-                            int32_t p1, int32_t p2, int32_t uniq, int32_t lr_tol, void* stream) {
-    MH_REQUIRE(left && right && ws && proxy, MH_ERR_ARG, "mh_sgm_proxy: null argument");
-    MH_REQUIRE(B > 0 && H > 0 && W > 0, MH_ERR_ARG, "mh_sgm_proxy: bad dimension");
-    MH_REQUIRE(H >= 7 && W >= 9, MH_ERR_ARG, "mh_sgm_proxy: the frame must hold one census window (H >= 7, W >= 9)");
-    MH_REQUIRE(D >= 1 && D <= 192 && D % 64 == 0, MH_ERR_UNSUPPORTED, "mh_sgm_proxy: D must be 64, 128 or 192");
-    MH_REQUIRE(p1 > 0 && p1 <= p2, MH_ERR_ARG, "mh_sgm_proxy: penalties must satisfy 0 < p1 <= p2");
-    MH_REQUIRE(64 + p2 <= 255, MH_ERR_ARG, "mh_sgm_proxy: 64 + p2 must fit 8 bits (the path volumes are uint8)");
-    MH_REQUIRE(uniq > 0 && uniq <= 100, MH_ERR_ARG, "mh_sgm_proxy: uniq must lie in 1 .. 100");
-    MH_REQUIRE(lr_tol >= 0, MH_ERR_ARG, "mh_sgm_proxy: lr_tol must not be negative");
-    MH_REQUIRE(mh_aligned16(ws), MH_ERR_ALIGN, "mh_sgm_proxy: ws must be 16-byte aligned");
-    MH_REQUIRE((int64_t)B * H * W < (1ll << 31) - 256 && B < 32768 && H < 65536 * SGM_CT_H, MH_ERR_UNSUPPORTED, "mh_sgm_proxy: too many pixels or frames");
+static inline int64_t sgm_align16(int64_t n) { return (n + 15) / 16 * 16; }
+
+extern "C" int64_t mh_sgm_ws_bytes_ex(int32_t B, int32_t H, int32_t W, int32_t D, int32_t paths, int32_t median) {
+    if (B <= 0 || H <= 0 || W <= 0 || D <= 0 || (paths != 4 && paths != 8) || (median != 0 && median != 1)) return 0;
+    const int64_t npix = (int64_t)B * H * W;
+    return sgm_align16(2 * npix * 8) + paths * sgm_align16(npix * D) + (paths == 8 ? sgm_align16(npix * D * 2) : 0) + sgm_align16(npix)
+           + (median ? sgm_align16(npix * 4) : 0);
+}
+
+extern "C" int64_t mh_sgm_ws_bytes(int32_t B, int32_t H, int32_t W, int32_t D) { return mh_sgm_ws_bytes_ex(B, H, W, D, 4, 0); }
+
+// census, aggregation, right view, select of one call: K = D / 64 disparities per lane, P paths
+template <int K, int P>
+static int sgm_launch(const SgmArgs& a, hipStream_t s) {
+    const int64_t npix = a.npix;
+    hipLaunchKernelGGL(sgm_census_kernel, dim3((unsigned)mh_cdiv(a.W, SGM_CT_W), (unsigned)mh_cdiv(a.H, SGM_CT_H), (unsigned)(2 * a.B)), dim3(256), 0, s, a);
+    if (int e = mh_check_launch("sgm_census")) return e;
+    const int nlines = 2 * a.H + 2 * a.W + (P == 8 ? 4 * (a.H + a.W - 1) : 0);
+    hipLaunchKernelGGL((sgm_paths_kernel<K, P>), dim3((unsigned)nlines, (unsigned)a.B), dim3(64), 0, s, a);
+    if (int e = mh_check_launch("sgm_paths")) return e;
+    if (P == 8) {
+        const int64_t n8 = npix * a.D / 8;                              // D is a multiple of 64; < 2^31 * 24
+        hipLaunchKernelGGL(sgm_fold_kernel, dim3((unsigned)mh_cdiv(n8, 256)), dim3(256), 0, s, a, n8);
+        if (int e = mh_check_launch("sgm_fold")) return e;
+    }
+    hipLaunchKernelGGL(sgm_right_kernel<P>, dim3((unsigned)mh_cdiv(npix, 256)), dim3(256), 0, s, a);
+    if (int e = mh_check_launch("sgm_right")) return e;
+    hipLaunchKernelGGL((sgm_select_kernel<K, P>), dim3((unsigned)mh_cdiv(npix, 4)), dim3(256), 0, s, a);
+    mh_note_kernel("sgm_paths_kernel<%d, %d> grid %d x %d", K, P, nlines, a.B);
+    return mh_check_launch("sgm_select");
+}
+
+// the one host function behind both entries; `who` names the entry in the messages
+static int sgm_proxy_impl(const char* who, const void* left, const void* right, int32_t frames_u8, void* ws, float* proxy, int32_t B, int32_t H, int32_t W, int32_t D,
+                          int32_t p1, int32_t p2, int32_t uniq, int32_t lr_tol, int32_t paths, int32_t median, void* stream) {
+    MH_REQUIRE(left && right && ws && proxy, MH_ERR_ARG, "%s: null argument", who);
+    MH_REQUIRE(B > 0 && H > 0 && W > 0, MH_ERR_ARG, "%s: bad dimension", who);
+    MH_REQUIRE(H >= 7 && W >= 9, MH_ERR_ARG, "%s: the frame must hold one census window (H >= 7, W >= 9)", who);
+    MH_REQUIRE(D >= 1 && D <= 192 && D % 64 == 0, MH_ERR_UNSUPPORTED, "%s: D must be 64, 128 or 192", who);
+    MH_REQUIRE(p1 > 0 && p1 <= p2, MH_ERR_ARG, "%s: penalties must satisfy 0 < p1 <= p2", who);
+    MH_REQUIRE(64 + p2 <= 255, MH_ERR_ARG, "%s: 64 + p2 must fit 8 bits (the path volumes are uint8)", who);
+    MH_REQUIRE(uniq > 0 && uniq <= 100, MH_ERR_ARG, "%s: uniq must lie in 1 .. 100", who);
+    MH_REQUIRE(lr_tol >= 0, MH_ERR_ARG, "%s: lr_tol must not be negative", who);
+    MH_REQUIRE(paths == 4 || paths == 8, MH_ERR_ARG, "%s: paths must be 4 or 8", who);
+    MH_REQUIRE(median == 0 || median == 1, MH_ERR_ARG, "%s: median must be 0 or 1", who);
+    MH_REQUIRE(mh_aligned16(ws), MH_ERR_ALIGN, "%s: ws must be 16-byte aligned", who);
+    MH_REQUIRE((int64_t)B * H * W < (1ll << 31) - 256 && B < 32768 && H < 65536 * SGM_CT_H, MH_ERR_UNSUPPORTED, "%s: too many pixels or frames", who);
     SgmArgs a{};
     const int64_t npix = (int64_t)B * H * W;
     a.left = left; a.right = right;
     a.census = (unsigned long long*)ws;
     a.vol = (unsigned char*)ws + sgm_align16(2 * npix * 8);
     a.vstride = sgm_align16(npix * D);
-    a.dr = a.vol + 4 * a.vstride;
-    a.out = proxy;
+    a.fold = (unsigned short*)(a.vol + paths * a.vstride);             // read only by the P = 8 kernels
+    a.dr = a.vol + paths * a.vstride + (paths == 8 ? sgm_align16(npix * D * 2) : 0);
+    float* raw = (float*)(a.dr + sgm_align16(npix));                   // the labels in front of the median (only with median)
+    a.out = median ? raw : proxy;
     a.B = B; a.H = H; a.W = W; a.D = D; a.u8 = frames_u8 ? 1 : 0; a.p1 = p1; a.p2 = p2; a.uniq = uniq; a.lr_tol = lr_tol; a.npix = (int)npix;
     hipStream_t s = (hipStream_t)stream;
-    hipLaunchKernelGGL(sgm_census_kernel, dim3((unsigned)mh_cdiv(W, SGM_CT_W), (unsigned)mh_cdiv(H, SGM_CT_H), (unsigned)(2 * B)), dim3(256), 0, s, a);
-    if (int e = mh_check_launch("sgm_census")) return e;
-    const dim3 lines((unsigned)(2 * H + 2 * W), (unsigned)B), pixels((unsigned)mh_cdiv(npix, 4));
-    switch (D / 64) {
-        case 1: hipLaunchKernelGGL(sgm_paths_kernel<1>, lines, dim3(64), 0, s, a); break;
-        case 2: hipLaunchKernelGGL(sgm_paths_kernel<2>, lines, dim3(64), 0, s, a); break;
-        default: hipLaunchKernelGGL(sgm_paths_kernel<3>, lines, dim3(64), 0, s, a); break;
+    int e;
+    switch (D / 64 * 16 + paths) {
+        case 16 + 4: e = sgm_launch<1, 4>(a, s); break;
+        case 32 + 4: e = sgm_launch<2, 4>(a, s); break;
+        case 48 + 4: e = sgm_launch<3, 4>(a, s); break;
+        case 16 + 8: e = sgm_launch<1, 8>(a, s); break;
+        case 32 + 8: e = sgm_launch<2, 8>(a, s); break;
+        default: e = sgm_launch<3, 8>(a, s); break;
     }
-    if (int e = mh_check_launch("sgm_paths")) return e;
-    hipLaunchKernelGGL(sgm_right_kernel, dim3((unsigned)mh_cdiv(npix, 256)), dim3(256), 0, s, a);
-    if (int e = mh_check_launch("sgm_right")) return e;
-    switch (D / 64) {
-        case 1: hipLaunchKernelGGL(sgm_select_kernel<1>, pixels, dim3(256), 0, s, a); break;
-        case 2: hipLaunchKernelGGL(sgm_select_kernel<2>, pixels, dim3(256), 0, s, a); break;
-        default: hipLaunchKernelGGL(sgm_select_kernel<3>, pixels, dim3(256), 0, s, a); break;
-    }
-    mh_note_kernel("sgm_paths_kernel<%d> grid %d x %d, 4 launches", D / 64, 2 * H + 2 * W, B);
-    return mh_check_launch("sgm_select");
+    if (e || !median) return e;
+    hipLaunchKernelGGL(sgm_median_kernel, dim3((unsigned)mh_cdiv(npix, 256)), dim3(256), 0, s, (const float*)raw, proxy, H, W, (int)npix);
+    return mh_check_launch("sgm_median");
+}
+
+extern "C" int mh_sgm_proxy_ex(const void* left, const void* right, int32_t frames_u8, void* ws, float* proxy, int32_t B, int32_t H, int32_t W, int32_t D,
+                               int32_t p1, int32_t p2, int32_t uniq, int32_t lr_tol, int32_t paths, int32_t median, void* stream) {
+    return sgm_proxy_impl("mh_sgm_proxy_ex", left, right, frames_u8, ws, proxy, B, H, W, D, p1, p2, uniq, lr_tol, paths, median, stream);
+}
+
+extern "C" int mh_sgm_proxy(const void* left, const void* right, int32_t frames_u8, void* ws, float* proxy, int32_t B, int32_t H, int32_t W, int32_t D,
+                            int32_t p1, int32_t p2, int32_t uniq, int32_t lr_tol, void* stream) {
+    return sgm_proxy_impl("mh_sgm_proxy", left, right, frames_u8, ws, proxy, B, H, W, D, p1, p2, uniq, lr_tol, 4, 0, stream);
 }
 
 extern "C" int mh_resize_image_fwd(const float* in, float* out, int32_t B, int32_t Hi, int32_t Wi, int32_t C, int32_t Ho, int32_t Wo,

@@ -1,4 +1,4 @@
-"""Proxy labels for the continual loop from the frames themselves: census + four-path semi-global matching on the device (mh_sgm_proxy), where the reference
+"""Proxy labels for the continual loop from the frames themselves: census + four- or eight-path semi-global matching on the device (mh_sgm_proxy_ex), where the reference
 reads a fourth list column of disparity maps an external matcher wrote (README.MD:59-61).  Runs outside the captured step, like mh_frame_prepare: through
 Data_utils.data_reader.device_prefetcher(proxy_matcher=...) on the upload stream, a frame ahead of the step that consumes it."""
 import torch
@@ -8,13 +8,14 @@ from . import ops
 
 class ProxyMatcher(object):
     """Owns the matcher's workspace for one frame size.  compute(left, right) -> float32 [B,H,W] device tensor, 0 = no label; contiguous and 16-byte aligned, so
-    Adapter.step takes it through the step's input table without a copy."""
+    Adapter.step takes it through the step's input table without a copy.  paths = 8 adds the four diagonal aggregation paths (fewer gross errors on frames of
+    the workload's size, worse on frames a few dozen rows high: DESIGN.md), median = True a 3x3 median of the valid labels."""
 
-    def __init__(self, lib, B, H, W, max_disp=128, device='cuda', p1=10, p2=120, uniq=95, lr_tol=1):
+    def __init__(self, lib, B, H, W, max_disp=128, device='cuda', p1=10, p2=120, uniq=95, lr_tol=1, paths=4, median=False):
         self.lib, self.shape, self.max_disp = lib, (int(B), int(H), int(W)), int(max_disp)
-        self.params = dict(p1=int(p1), p2=int(p2), uniq=int(uniq), lr_tol=int(lr_tol))
+        self.params = dict(p1=int(p1), p2=int(p2), uniq=int(uniq), lr_tol=int(lr_tol), paths=int(paths), median=bool(median))
         self.device = torch.device(device)
-        self.ws = ops.sgm_proxy_ws(lib, B, H, W, self.max_disp, self.device)
+        self.ws = ops.sgm_proxy_ws(lib, B, H, W, self.max_disp, self.device, paths=paths, median=median)
 
     def new_output(self):
         return torch.empty(self.shape, dtype=torch.float32, device=self.device)

@@ -1,4 +1,5 @@
-"""The on-device proxy matcher (mh_sgm_proxy) on KITTI size, and the continual loop with and without it.   usage: python scripts/exp/sgm_proxy_bench.py MODE
+"""The on-device proxy matcher (mh_sgm_proxy) on KITTI size, and the continual loop with and without it.
+usage: python scripts/exp/sgm_proxy_bench.py MODE [--paths {4,8}] [--median]      (the matcher's options, for total / kernels / loop)
   total    1 x 375 x 1242, D = 128: workspace bytes, wall time of one call (events around 100 calls, after 20), uint8 and float32 frames
   kernels  the same calls and nothing else -- run it under `rocprofv3 --kernel-trace --stats` for the time per kernel
   loop     Adapter.step (MADNet, MAD and FULL, 320 x 1216 resident frames, 200 steps after 20): alone / with the matcher of the NEXT frame on a second stream
@@ -15,7 +16,15 @@ import torch
 from madnet_hip import _ffi, engine as E, synthetic as S
 from madnet_hip.proxy import ProxyMatcher
 
-mode = sys.argv[1] if len(sys.argv) > 1 else "total"
+argv = sys.argv[1:]
+median = "--median" in argv
+if median:
+    argv.remove("--median")
+paths = 4
+if "--paths" in argv:
+    paths = int(argv[argv.index("--paths") + 1])
+    del argv[argv.index("--paths"):argv.index("--paths") + 2]
+mode = argv[0] if argv else "total"
 lib = _ffi.lib()
 
 
@@ -23,7 +32,7 @@ def matcher_calls(n, warm, dtype):
     H, W, D = 375, 1242, 128
     l, r, _ = S.make_pair(H, W)
     tl, tr = (torch.from_numpy(a.astype(dtype)).cuda() for a in (l, r))
-    m = ProxyMatcher(lib, 1, H, W, max_disp=D)
+    m = ProxyMatcher(lib, 1, H, W, max_disp=D, paths=paths, median=median)
     out = m.new_output()
     for _ in range(warm):
         m.compute(tl, tr, out=out)
@@ -40,8 +49,8 @@ if mode in ("total", "kernels"):
     for dtype in (np.uint8, np.float32):
         m, out, ts = matcher_calls(100, 20, dtype)
         if mode == "total":
-            print("mh_sgm_proxy 1x375x1242 D=128 %-7s workspace %.1f MB   one call: median %.3f ms, min %.3f, max %.3f   valid share %.3f"
-                  % (np.dtype(dtype).name, m.ws.numel() / 1e6, np.median(ts), ts.min(), ts.max(), float((out > 0).float().mean())))
+            print("mh_sgm_proxy 1x375x1242 D=128 paths %d median %d %-7s workspace %.1f MB   one call: median %.3f ms, min %.3f, max %.3f   valid share %.3f"
+                  % (paths, median, np.dtype(dtype).name, m.ws.numel() / 1e6, np.median(ts), ts.min(), ts.max(), float((out > 0).float().mean())))
 
 if mode == "loop":
     import Nets
@@ -51,7 +60,7 @@ if mode == "loop":
     pairs = [S.make_pair(H, W, stream_id=100, frame=t) for t in range(8)]
     z = torch.zeros(1, H, W, 3, device="cuda")
     frames = [tuple(torch.as_tensor(a, dtype=torch.float32, device="cuda") for a in (l, r, np.ascontiguousarray(g[..., 0]))) for l, r, g in pairs]
-    m = ProxyMatcher(lib, 1, H, W, max_disp=128)
+    m = ProxyMatcher(lib, 1, H, W, max_disp=128, paths=paths, median=median)
     side = torch.cuda.Stream()
     for amode in ("MAD", "FULL"):
         net = Nets.get_stereo_net("MADNet", {"left_img": z, "right_img": z, "split_layers": [None], "sequence": True, "train_portion": "BEGIN",
