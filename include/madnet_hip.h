@@ -444,6 +444,23 @@ int64_t mh_sgm_ws_bytes_ex(int32_t B, int32_t H, int32_t W, int32_t D, int32_t p
 int mh_sgm_proxy_ex(const void* left, const void* right, int32_t frames_u8, void* ws, float* proxy,
                     int32_t B, int32_t H, int32_t W, int32_t D, int32_t p1, int32_t p2, int32_t uniq, int32_t lr_tol,
                     int32_t paths, int32_t median, void* stream);
+/* Speckle filter of a finished label map, the last stage of an SGM pipeline (additive: the ABI version stays).  labels, out: [B][H][W] float32.
+ *   Valid pixels: a pixel is valid when label > 0; NaN, 0 and negative labels are not.
+ *   Connectivity: two pixels are connected when they are 4-neighbours inside the same frame (no row wrap, nothing from the next image of a batch), both are valid
+ *      and fabsf(a - b) <= max_diff, the difference rounded once to float32.
+ *   Components: the transitive closure of that relation; a chain a-b-c is one component even when |a - c| > max_diff.
+ *   Output: out[p] = labels[p], bit for bit, when p is valid and its component holds MORE than max_size pixels, else 0.  Every element of out is written;
+ *      out == labels is allowed; max_size == 0 keeps every valid label.
+ *   Limits: B, H, W > 0, max_size >= 0, max_diff finite and >= 0 (MH_ERR_ARG); ws 16-byte aligned (MH_ERR_ALIGN); B * H * W < 2^31 - 256, B < 65536,
+ *      H < 2^20 (MH_ERR_UNSUPPORTED).  On a violation nothing is launched.
+ * ws: mh_sgm_speckle_ws_bytes bytes (0 for a non-positive dimension): parent [B][H][W] (int32) | count [B][H][W] (int32), each rounded up to 16 bytes.  The caller
+ * does not initialise it, the op never reads what it has not written in the same call, and no byte behind the stated size is touched.
+ * Deterministic: components are joined with integer atomicMin and counted with integer atomicAdd, a component's root is its lowest pixel and its count an integer
+ * sum -- the result is a function of the input only, two calls give the same bits, there are no float atomics.
+ * Four launches on `stream` (two when the frame fits one 64 x 16 tile); called directly, never part of a plan. */
+int64_t mh_sgm_speckle_ws_bytes(int32_t B, int32_t H, int32_t W);
+int mh_sgm_speckle(const float* labels, float* out, void* ws, int32_t B, int32_t H, int32_t W,
+                   int32_t max_size, float max_diff, void* stream);
 
 /* ---- preprocessing.pad_image (REFLECT, preprocessing.py:7-29) fused with the float cast
  *      and the channel padding 3 -> out_ld (extra channels zero) ------------------------ */

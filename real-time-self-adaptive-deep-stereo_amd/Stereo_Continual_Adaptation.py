@@ -63,7 +63,8 @@ def main(args):
         if args.proxies == 'sgm':
             # the proxy labels of every frame from the frame itself: census + semi-global matching on the prefetcher's upload stream (madnet_hip/proxy.py)
             from madnet_hip.proxy import ProxyMatcher
-            matcher = ProxyMatcher(adapter.lib, 1, H, W, max_disp=args.proxyMaxDisp, device=dev, paths=args.proxyPaths, median=args.proxyMedian)
+            matcher = ProxyMatcher(adapter.lib, 1, H, W, max_disp=args.proxyMaxDisp, device=dev, paths=args.proxyPaths, median=args.proxyMedian,
+                                   speckle_size=args.proxySpeckle, speckle_range=args.proxySpeckleRange)
         frames = data_reader.device_prefetcher(data_set, dev, depth=3, consumer_stream=adapter.stream, cast=False, proxy_matcher=matcher)
         for left, right, gt, proxy, real_width in frames:
             out = adapter.step(left, right, gt[..., 0], proxy=proxy if matcher is not None else proxy[..., 0])
@@ -132,10 +133,12 @@ def build_parser():
     parser.add_argument("--decay", help="multiplicative decay of the sampling logits", type=float, default=0.99)
     parser.add_argument("--uf", help="gain of the reward added to the logits of the last trained portions", type=float, default=0.01)
     parser.add_argument("--precision", help="MFMA arithmetic of the conv kernels: fp32 (default; the reference adapts in fp32), mixed (forward within fp32 tolerance, bf16 gradients) or bf16 (opt-in throughput mode)", choices=['fp32', 'mixed', 'bf16'], default='fp32')
-    parser.add_argument("--proxies", help="where the proxy labels come from: list = the fourth column of the list (disparity PNGs of an external matcher); sgm = computed on the GPU from every frame pair (census + four-path semi-global matching; --proxyPaths 8 adds the diagonal paths, --proxyMedian a 3x3 median of the labels), the list then needs only left,right,gt", choices=['list', 'sgm'], default='list')
+    parser.add_argument("--proxies", help="where the proxy labels come from: list = the fourth column of the list (disparity PNGs of an external matcher); sgm = computed on the GPU from every frame pair (census + four-path semi-global matching; --proxyPaths 8 adds the diagonal paths, --proxyMedian a 3x3 median of the labels, --proxySpeckle N a speckle filter), the list then needs only left,right,gt", choices=['list', 'sgm'], default='list')
     parser.add_argument("--proxyMaxDisp", help="--proxies sgm: number of disparities searched (64, 128 or 192)", type=int, default=128)
     parser.add_argument("--proxyPaths", help="--proxies sgm: aggregation paths, 4 = rows and columns, 8 = the four diagonals as well (fewer gross errors on full-size frames, worse on frames a few dozen rows high)", type=int, choices=[4, 8], default=4)
     parser.add_argument("--proxyMedian", help="--proxies sgm: 3x3 median of the valid labels", action='store_true')
+    parser.add_argument("--proxySpeckle", help="--proxies sgm: speckle filter, labels in 4-connected components of at most N pixels are dropped (0 = off; removes a fifth of the labels on frames a few dozen rows high)", type=int, default=0)
+    parser.add_argument("--proxySpeckleRange", help="--proxies sgm: largest disparity difference between neighbouring pixels of one component of the speckle filter", type=float, default=1.0)
     parser.add_argument("--dumpOutputs", help="also write the float32 disparity of every frame to <output>/disparities/disparity_<step>.npy", action='store_true')
     return parser
 

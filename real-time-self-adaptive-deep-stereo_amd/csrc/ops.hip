@@ -1751,6 +1751,207 @@ extern "C" int mh_sgm_proxy(const void* left, const void* right, int32_t frames_
     return sgm_proxy_impl("mh_sgm_proxy", left, right, frames_u8, ws, proxy, B, H, W, D, p1, p2, uniq, lr_tol, 4, 0, stream);
 }
 
+// ---- speckle filter of a finished label map (mh_sgm_speckle): 4-connected components of the valid labels, the small ones set to 0 ------------------------------------
+// Four launches, each reading only what an EARLIER launch (or itself, through atomics) wrote -- a kernel boundary is the one free coherence point between workgroups:
+//   1. sgm_speckle_tile_kernel: components of one 64 x 16 tile by union-find in LDS; parent[p] = the tile-local root (the lowest pixel of the piece, itself for a root,
+//      -1 for an invalid pixel), cnt[p] = the piece's pixel count at its root, 0 elsewhere.
+//   2. sgm_speckle_merge_kernel: one thread per pixel pair across a tile border; joins the two roots.  Every access to `parent` in this launch is an integer atomic,
+//      which executes at the memory side: no decision is taken on a cached word.
+//   3. sgm_speckle_count_kernel: every tile-local root that is no longer a root adds its count to its final root (integer atomicAdd: associative, so the order of
+//      arrival cannot change the sum) and leaves -(root + 1) in its own cnt.
+//   4. sgm_speckle_apply_kernel: out = the label where its component's count exceeds max_size, else 0.
+// Invariant of `parent` from launch 1 on: parent[p] <= p, parent[p] lies in p's component, and a word only ever decreases (atomicMin).  A walk up the parents
+// therefore strictly decreases until it meets a root, whatever the other threads do meanwhile.  The final root of a component is its lowest pixel, the counts are
+// integer sums: the result is a function of the input alone.
+// ws: parent [B][H][W] (int32) | cnt [B][H][W] (int32), each rounded up to 16 bytes.  Every word is written by launch 1 before anything reads it.
+#define SGM_ST_W 64
+#define SGM_ST_H 16
+#define SGM_ST_N (SGM_ST_W * SGM_ST_H)
+
+#ifndef __HIPCC__
+// the CPU emulator's header has atomicAdd only; its workgroups run on several OS threads
+static inline int atomicMin(int* addr, int v) {
+    int old = __atomic_load_n(addr, __ATOMIC_RELAXED);
+    while (old > v && !__atomic_compare_exchange_n(addr, &old, v, false, __ATOMIC_RELAXED, __ATOMIC_RELAXED)) {}
+    return old;
+}
+#endif
+
+struct SpeckleArgs {
+    const float* in; float* out;         // may be the same map: not __restrict__
+    int* parent; int* cnt;
+    int B, H, W, npix, max_size, nvb, nhb;      // nvb, nhb: tile borders inside a frame, between columns and between rows
+    float max_diff;
+};
+
+__device__ __forceinline__ bool sgm_speckle_joined(float a, float b, float max_diff) { return a > 0.f && b > 0.f && fabsf(a - b) <= max_diff; }
+
+// Union-find over the tile's pixels in LDS.  lab[i] <= i, only ever lowered by atomicMin, always to a pixel of i's own component.
+// find: each step moves to a strictly lower index, so it ends; the word it read may have been lowered since, which makes the node it returns a non-root
+// ancestor at worst -- unite does not trust it: the atomicMin's own return value says whether the node was still a root.
+__device__ __forceinline__ int sgm_speckle_find_lds(int* lab, int x) {
+    for (;;) { const int p = __atomic_load_n(lab + x, __ATOMIC_RELAXED); if (p == x) return x; x = p; }      // (atomic: a fresh ds_read per step, never a register copy)
+}
+// unite: joins the larger of the two found nodes to the smaller.  old == a: a was a root and now hangs under b, done.  Otherwise a had a parent `old` < a already:
+// lab[a] is now min(old, b), still inside the component, and what remains to be joined is (old, b).  max(a, b) strictly decreases per round: it ends.
+__device__ __forceinline__ void sgm_speckle_unite_lds(int* lab, int a, int b) {
+    for (;;) {
+        a = sgm_speckle_find_lds(lab, a); b = sgm_speckle_find_lds(lab, b);
+        if (a == b) return;
+        if (a < b) { const int t = a; a = b; b = t; }
+        const int old = atomicMin(lab + a, b);
+        if (old == a) return;
+        a = old;
+    }
+}
+
+// launch 1: grid (tiles x, tiles y, B), 256 threads, four pixels each (i = thread + 256 k: a wave covers one tile row)
+__global__ __launch_bounds__(256) void sgm_speckle_tile_kernel(SpeckleArgs a) {
+    __shared__ float s_v[SGM_ST_N];
+    __shared__ int s_lab[SGM_ST_N];
+    __shared__ int s_cnt[SGM_ST_N];
+    const int x0 = (int)blockIdx.x * SGM_ST_W, y0 = (int)blockIdx.y * SGM_ST_H;
+    const int frame = (int)blockIdx.z * a.H * a.W;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const int i = (int)threadIdx.x + 256 * k, x = x0 + (i & (SGM_ST_W - 1)), y = y0 + i / SGM_ST_W;
+        float v = 0.f;
+        if (x < a.W && y < a.H) v = a.in[frame + y * a.W + x];
+        s_v[i] = v > 0.f ? v : 0.f;                                     // NaN, 0, negative and outside the frame: 0 = joins nothing
+        s_lab[i] = i; s_cnt[i] = 0;
+    }
+    __syncthreads();
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const int i = (int)threadIdx.x + 256 * k;
+        const float v = s_v[i];
+        if ((i & (SGM_ST_W - 1)) < SGM_ST_W - 1 && sgm_speckle_joined(v, s_v[i + 1], a.max_diff)) sgm_speckle_unite_lds(s_lab, i, i + 1);
+        if (i < SGM_ST_N - SGM_ST_W && sgm_speckle_joined(v, s_v[i + SGM_ST_W], a.max_diff)) sgm_speckle_unite_lds(s_lab, i, i + SGM_ST_W);
+    }
+    __syncthreads();                                                    // s_lab is read-only from here: every find below returns the true root
+    int root[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const int i = (int)threadIdx.x + 256 * k;
+        root[k] = s_v[i] > 0.f ? sgm_speckle_find_lds(s_lab, i) : -1;
+        if (root[k] >= 0) atomicAdd(s_cnt + root[k], 1);
+    }
+    __syncthreads();
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const int i = (int)threadIdx.x + 256 * k, x = x0 + (i & (SGM_ST_W - 1)), y = y0 + i / SGM_ST_W;
+        if (x >= a.W || y >= a.H) continue;
+        const int g = frame + y * a.W + x, r = root[k];
+        a.parent[g] = r < 0 ? -1 : frame + (y0 + r / SGM_ST_W) * a.W + x0 + (r & (SGM_ST_W - 1));
+        a.cnt[g] = r == i ? s_cnt[i] : 0;
+    }
+}
+
+// The same union-find on the global `parent`, between workgroups of one launch.  A read is atomicMin(parent + x, x): parent[x] <= x makes it change nothing, and
+// as a read-modify-write it is answered by the memory side with the word's present value, never by this CU's L1 or a register.  Termination as in LDS; the
+// decisions (p == x, old == a) are taken on values the atomics returned.
+__device__ __forceinline__ int sgm_speckle_find_atomic(int* parent, int x) {
+    for (;;) { const int p = atomicMin(parent + x, x); if (p == x) return x; x = p; }
+}
+
+// the tile-local root of pixel x as launch 1 left it, from words this launch never writes: cnt (launch 3 writes it next) and the parent of a pixel that is no
+// tile-local root (only roots are ever linked)
+__device__ __forceinline__ int sgm_speckle_local_root(const SpeckleArgs& a, int x) { return a.cnt[x] > 0 ? x : a.parent[x]; }
+
+// launch 2: one thread per pixel pair across a tile border, grid (pairs / 256, B): first the nvb column borders (H pairs each), then the nhb row borders (W pairs each).
+// Neighbouring pairs of one border mostly join the same two tile-local pieces, and a large component would send every one of them up to the same root word: a pair
+// whose predecessor along the border is joined too and has the same two tile-local roots leaves the work to it (by induction the first pair of such a run does it).
+__global__ __launch_bounds__(256) void sgm_speckle_merge_kernel(SpeckleArgs a) {
+    int e = (int)blockIdx.x * 256 + (int)threadIdx.x;
+    const int frame = (int)blockIdx.y * a.H * a.W;
+    int p, q, back;                                                     // back: the distance to the predecessor pair, 0 = none
+    if (e < a.nvb * a.H) { const int bx = e / a.H, y = e - bx * a.H; q = frame + y * a.W + (bx + 1) * SGM_ST_W; p = q - 1; back = y ? a.W : 0; }
+    else {
+        e -= a.nvb * a.H;
+        if (e >= a.nhb * a.W) return;
+        const int by = e / a.W, x = e - by * a.W;
+        q = frame + (by + 1) * SGM_ST_H * a.W + x; p = q - a.W; back = x ? 1 : 0;
+    }
+    if (!sgm_speckle_joined(a.in[p], a.in[q], a.max_diff)) return;
+    const int pp = p - back, pq = q - back;
+    p = sgm_speckle_local_root(a, p); q = sgm_speckle_local_root(a, q);
+    if (back && sgm_speckle_joined(a.in[pp], a.in[pq], a.max_diff) && sgm_speckle_local_root(a, pp) == p && sgm_speckle_local_root(a, pq) == q) return;
+    for (;;) {
+        p = sgm_speckle_find_atomic(a.parent, p); q = sgm_speckle_find_atomic(a.parent, q);
+        if (p == q) return;
+        if (p < q) { const int t = p; p = q; q = t; }
+        const int old = atomicMin(a.parent + p, q);
+        if (old == p) return;
+        p = old;
+    }
+}
+
+// launches 3 and 4 only read `parent`: the walk ends at the component's root
+__device__ __forceinline__ int sgm_speckle_find(const int* __restrict__ parent, int x) {
+    for (;;) { const int p = parent[x]; if (p == x) return x; x = p; }
+}
+
+// launch 3: one thread per pixel.  c > 0 marks a tile-local root.  One that is not its component's root is never the target of an add (adds go to roots only), so the
+// c it read is exact, and its cnt word is its own to overwrite.  A root may read its own count while adds arrive; any value it can see is > 0 and it does nothing.
+__global__ __launch_bounds__(256) void sgm_speckle_count_kernel(SpeckleArgs a) {
+    const int p = (int)blockIdx.x * 256 + (int)threadIdx.x;
+    if (p >= a.npix) return;
+    const int c = a.cnt[p];
+    if (c <= 0) return;
+    const int r = sgm_speckle_find(a.parent, p);
+    if (r == p) return;
+    atomicAdd(a.cnt + r, c);
+    a.cnt[p] = -(r + 1);
+}
+
+// launch 4: one thread per pixel; every element of out is written.  A pixel that is no tile-local root (cnt 0) has its tile-local root as parent.
+__global__ __launch_bounds__(256) void sgm_speckle_apply_kernel(SpeckleArgs a) {
+    const int p = (int)blockIdx.x * 256 + (int)threadIdx.x;
+    if (p >= a.npix) return;
+    const float v = a.in[p];
+    float o = 0.f;
+    if (v > 0.f) {
+        int n = a.cnt[p];
+        if (n == 0) n = a.cnt[a.parent[p]];
+        if (n < 0) n = a.cnt[-n - 1];
+        if (n > a.max_size) o = v;
+    }
+    a.out[p] = o;
+}
+
+extern "C" int64_t mh_sgm_speckle_ws_bytes(int32_t B, int32_t H, int32_t W) {
+    if (B <= 0 || H <= 0 || W <= 0) return 0;
+    return 2 * sgm_align16((int64_t)B * H * W * 4);
+}
+
+extern "C" int mh_sgm_speckle(const float* labels, float* out, void* ws, int32_t B, int32_t H, int32_t W, int32_t max_size, float max_diff, void* stream) {
+    MH_REQUIRE(labels && out && ws, MH_ERR_ARG, "mh_sgm_speckle: null argument");
+    MH_REQUIRE(B > 0 && H > 0 && W > 0, MH_ERR_ARG, "mh_sgm_speckle: bad dimension");
+    MH_REQUIRE(max_size >= 0, MH_ERR_ARG, "mh_sgm_speckle: max_size must not be negative");
+    MH_REQUIRE(max_diff >= 0.f && max_diff < __builtin_inff(), MH_ERR_ARG, "mh_sgm_speckle: max_diff must be finite and not negative");
+    MH_REQUIRE(mh_aligned16(ws), MH_ERR_ALIGN, "mh_sgm_speckle: ws must be 16-byte aligned");
+    MH_REQUIRE((int64_t)B * H * W < (1ll << 31) - 256 && B < 65536 && H < 65536 * SGM_ST_H, MH_ERR_UNSUPPORTED, "mh_sgm_speckle: too many pixels or frames");
+    const int64_t npix = (int64_t)B * H * W;
+    SpeckleArgs a{};
+    a.in = labels; a.out = out;
+    a.parent = (int*)ws; a.cnt = (int*)((char*)ws + sgm_align16(npix * 4));
+    a.B = B; a.H = H; a.W = W; a.npix = (int)npix; a.max_size = max_size; a.max_diff = max_diff;
+    a.nvb = (W - 1) / SGM_ST_W; a.nhb = (H - 1) / SGM_ST_H;
+    hipStream_t s = (hipStream_t)stream;
+    hipLaunchKernelGGL(sgm_speckle_tile_kernel, dim3((unsigned)mh_cdiv(W, SGM_ST_W), (unsigned)mh_cdiv(H, SGM_ST_H), (unsigned)B), dim3(256), 0, s, a);
+    if (int e = mh_check_launch("sgm_speckle_tile")) return e;
+    const int64_t pairs = (int64_t)a.nvb * H + (int64_t)a.nhb * W;     // < 2 H W / 16
+    if (pairs > 0) {
+        hipLaunchKernelGGL(sgm_speckle_merge_kernel, dim3((unsigned)mh_cdiv(pairs, 256), (unsigned)B), dim3(256), 0, s, a);
+        if (int e = mh_check_launch("sgm_speckle_merge")) return e;
+        hipLaunchKernelGGL(sgm_speckle_count_kernel, dim3((unsigned)mh_cdiv(npix, 256)), dim3(256), 0, s, a);
+        if (int e = mh_check_launch("sgm_speckle_count")) return e;
+    }
+    hipLaunchKernelGGL(sgm_speckle_apply_kernel, dim3((unsigned)mh_cdiv(npix, 256)), dim3(256), 0, s, a);
+    mh_note_kernel("sgm_speckle_tile_kernel grid %d x %d x %d, %d launches", mh_cdiv(W, SGM_ST_W), mh_cdiv(H, SGM_ST_H), B, pairs > 0 ? 4 : 2);
+    return mh_check_launch("sgm_speckle_apply");
+}
+
 extern "C" int mh_resize_image_fwd(const float* in, float* out, int32_t B, int32_t Hi, int32_t Wi, int32_t C, int32_t Ho, int32_t Wo,
                                    void* stream) {
     MH_REQUIRE(in && out && B > 0 && Hi > 0 && Wi > 0 && C > 0 && Ho > 0 && Wo > 0, MH_ERR_ARG, "mh_resize_image_fwd: bad argument");

@@ -839,6 +839,22 @@ def sgm_proxy(lib, left, right, ws, out, max_disp=128, p1=10, p2=120, uniq=95, l
     return out
 
 
+def sgm_speckle_ws(lib, B, H, W, device):
+    """the workspace of sgm_speckle (a parent and a count word per pixel); torch allocations are at least 16-byte aligned"""
+    return torch.empty(int(lib.sgm_speckle_ws_bytes(B, H, W)), dtype=torch.uint8, device=device)
+
+
+def sgm_speckle(lib, labels, out, ws, max_size, max_diff=1.0, stream=None):
+    """labels [B,H,W] float32 -> out: the labels of the 4-connected components (valid = label > 0, neighbours within max_diff) that hold more than max_size
+    pixels, 0 elsewhere (mh_sgm_speckle).  out may be labels.  Called directly, never recorded."""
+    assert labels.dim() == 3 and labels.dtype == torch.float32 and labels.is_contiguous(), "sgm_speckle: [B,H,W] float32"
+    B, H, W = labels.shape
+    assert out.is_contiguous() and out.dtype == torch.float32 and out.numel() == B * H * W and out.device == labels.device
+    assert ws.numel() * ws.element_size() >= lib.sgm_speckle_ws_bytes(B, H, W), "sgm_speckle: workspace too small"
+    lib.sgm_speckle(_p(labels), _p(out), _p(ws), B, H, W, int(max_size), float(max_diff), _p(stream))
+    return out
+
+
 def proxy_loss_scaled(lib, pred, proxy, ws, result, scale, dpred=None, weight=0.1, grad_scale=1.0, stream=None):
     """proxy_loss of the prediction and the proxy labels both resized to (H // scale, W // scale), the labels divided by scale (a MAD block's loss under
     --reprojectionScale, Stereo_Continual_Adaptation.py:95-112) in one op; dpred = its gradient on the full-size grid (optional).  ws: proxy_scaled_ws_floats."""

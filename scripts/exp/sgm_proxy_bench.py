@@ -1,7 +1,9 @@
 """The on-device proxy matcher (mh_sgm_proxy) on KITTI size, and the continual loop with and without it.
-usage: python scripts/exp/sgm_proxy_bench.py MODE [--paths {4,8}] [--median]      (the matcher's options, for total / kernels / loop)
+usage: python scripts/exp/sgm_proxy_bench.py MODE [--paths {4,8}] [--median] [--speckle N]      (the matcher's options, for total / kernels / loop / speckle)
   total    1 x 375 x 1242, D = 128: workspace bytes, wall time of one call (events around 100 calls, after 20), uint8 and float32 frames
   kernels  the same calls and nothing else -- run it under `rocprofv3 --kernel-trace --stats` for the time per kernel
+  speckle  the same call without and with the speckle filter (--speckle N, default 100, range 1.0), alternating in blocks of 100 calls, three rounds after a
+           warm-up of both, one process: the filter's cost is the difference of the medians; and the filter alone on the matcher's labels
   loop     Adapter.step (MADNet, MAD and FULL, 320 x 1216 resident frames, 200 steps after 20): alone / with the matcher of the NEXT frame on a second stream
            in front of an event the step waits for (the prefetcher's position)
   script   Stereo_Continual_Adaptation.py --proxies list against --proxies sgm on the same 220-row list (8 distinct 375 x 1242 frames as PNGs, cropped to
@@ -24,7 +26,13 @@ paths = 4
 if "--paths" in argv:
     paths = int(argv[argv.index("--paths") + 1])
     del argv[argv.index("--paths"):argv.index("--paths") + 2]
+speckle = 0
+if "--speckle" in argv:
+    speckle = int(argv[argv.index("--speckle") + 1])
+    del argv[argv.index("--speckle"):argv.index("--speckle") + 2]
 mode = argv[0] if argv else "total"
+if mode == "speckle" and not speckle:
+    speckle = 100
 lib = _ffi.lib()
 
 
@@ -32,7 +40,7 @@ def matcher_calls(n, warm, dtype):
     H, W, D = 375, 1242, 128
     l, r, _ = S.make_pair(H, W)
     tl, tr = (torch.from_numpy(a.astype(dtype)).cuda() for a in (l, r))
-    m = ProxyMatcher(lib, 1, H, W, max_disp=D, paths=paths, median=median)
+    m = ProxyMatcher(lib, 1, H, W, max_disp=D, paths=paths, median=median, speckle_size=speckle)
     out = m.new_output()
     for _ in range(warm):
         m.compute(tl, tr, out=out)
@@ -51,6 +59,41 @@ if mode in ("total", "kernels"):
         if mode == "total":
             print("mh_sgm_proxy 1x375x1242 D=128 paths %d median %d %-7s workspace %.1f MB   one call: median %.3f ms, min %.3f, max %.3f   valid share %.3f"
                   % (paths, median, np.dtype(dtype).name, m.ws.numel() / 1e6, np.median(ts), ts.min(), ts.max(), float((out > 0).float().mean())))
+
+
+def timed(fn, n):
+    ts = []
+    for _ in range(n):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record(); fn(); e1.record(); e1.synchronize()
+        ts.append(e0.elapsed_time(e1))
+    return np.asarray(ts)
+
+
+if mode == "speckle":
+    from madnet_hip import ops
+    H, W, D = 375, 1242, 128
+    l, r, _ = S.make_pair(H, W)
+    tl, tr = (torch.from_numpy(a.astype(np.uint8)).cuda() for a in (l, r))
+    plain = ProxyMatcher(lib, 1, H, W, max_disp=D, paths=paths, median=median)
+    filt = ProxyMatcher(lib, 1, H, W, max_disp=D, paths=paths, median=median, speckle_size=speckle)
+    o0, o1, o2 = plain.new_output(), filt.new_output(), filt.new_output()
+    runs = {"matcher alone": lambda: plain.compute(tl, tr, out=o0), "matcher + speckle": lambda: filt.compute(tl, tr, out=o1),
+            "speckle alone": lambda: ops.sgm_speckle(lib, o0, o2, filt.speckle_ws, speckle, 1.0)}
+    for fn in runs.values():
+        timed(fn, 20)
+    torch.cuda.synchronize()
+    assert torch.equal(o1, o2), "the filter behind the matcher and the filter on the matcher's labels differ"
+    print("1x375x1242 D=128 paths %d median %d uint8, speckle filter (%d, 1.0): filter workspace %.1f MB, valid share %.4f -> %.4f"
+          % (paths, median, speckle, filt.speckle_ws.numel() / 1e6, float((o0 > 0).float().mean()), float((o1 > 0).float().mean())))
+    for rnd in range(3):
+        med = {}
+        for name, fn in runs.items():
+            ts = timed(fn, 100)
+            med[name] = np.median(ts)
+            print("round %d  %-18s one call: median %.3f ms, min %.3f, max %.3f" % (rnd, name, np.median(ts), ts.min(), ts.max()))
+        print("round %d  the filter adds %.3f ms = %.1f %% of the matcher" % (rnd, med["matcher + speckle"] - med["matcher alone"],
+              100.0 * (med["matcher + speckle"] - med["matcher alone"]) / med["matcher alone"])); sys.stdout.flush()
 
 if mode == "loop":
     import Nets
