@@ -444,6 +444,29 @@ int64_t mh_sgm_ws_bytes_ex(int32_t B, int32_t H, int32_t W, int32_t D, int32_t p
 int mh_sgm_proxy_ex(const void* left, const void* right, int32_t frames_u8, void* ws, float* proxy,
                     int32_t B, int32_t H, int32_t W, int32_t D, int32_t p1, int32_t p2, int32_t uniq, int32_t lr_tol,
                     int32_t paths, int32_t median, void* stream);
+/* mh_sgm_proxy_ex on frames of 1 / scale the size (additive: the ABI version stays).  scale = 1 is mh_sgm_proxy_ex and mh_sgm_ws_bytes_ex exactly: the same bits, the
+ * same bytes, the same launches.  scale = 2, on frames [B,H,W,3] with H >= 13 and W >= 17; D stays the FULL-RESOLUTION search range and must be 128, 256 or 384:
+ *   1. Half gray.  h = (H + 1) / 2, w = (W + 1) / 2.  Every full-resolution pixel gets the gray g of mh_sgm_proxy (float32 channels rounded to nearest and clamped
+ *      to 0 .. 255 first, then 77 R + 150 G + 29 B + 128 >> 8), and
+ *         g2(y, x) = (g(2y, 2x) + g(2y, x1) + g(y1, 2x) + g(y1, x1) + 2) >> 2,   x1 = min(2x + 1, W - 1),   y1 = min(2y + 1, H - 1).
+ *      Integer arithmetic throughout; nothing is read from the next image of a batch.
+ *   2. Match.  The matcher of mh_sgm_proxy_ex on the two [B,h,w] gray images as they are, with D / 2 disparities (64, 128 or 192) and the caller's p1, p2, uniq,
+ *      lr_tol, paths and median unchanged: census 9 x 7, Hamming cost, aggregation, uniqueness, left-right check, parabola, 3 x 3 median.  77 + 150 + 29 = 256, so
+ *      a gray image is its own gray: the stage is mh_sgm_proxy_ex on an RGB image whose three channels equal g2, bit for bit.  l = its labels [B,h,w].
+ *   3. Upsample.  proxy[b, y, x] = 2 l[b, y >> 1, x >> 1] where that label is > 0, else 0.  Nearest neighbour: nothing is averaged, a valid label never mixes with
+ *      a rejected one, and the doubling is exact in float32.  Every element of `proxy` is written.
+ * The labels are about twice as far from the truth as those of scale 1 and clearly worse on frames a few dozen rows high: an option, like eight paths.
+ * ws at scale 2, mh_sgm_ws_bytes_scaled bytes, 16-byte aligned, in this order, each part rounded up to 16 bytes: the half grays [2][B][h][w] (uint8, left view
+ * first) | mh_sgm_ws_bytes_ex(B, h, w, D / 2, paths, median) bytes laid out as above | the half-resolution labels [B][h][w] (float32).  No byte behind the stated
+ * size is touched.
+ * MH_ERR_ARG, nothing launched: a scale other than 1 or 2; a D that is illegal for the scale (scale 1: 64, 128, 192); a frame too small for the scale; an illegal
+ * option; every other violation has the code of mh_sgm_proxy_ex (at scale 2 also H > 262140: MH_ERR_UNSUPPORTED).  mh_sgm_ws_bytes_scaled is 0 in the same cases (at scale 1: where mh_sgm_ws_bytes_ex is 0).
+ * No atomics, two calls give the same bits.  Launches at scale 2: those of mh_sgm_proxy_ex on the half frame (four, one more for eight paths, one more with the
+ * median) plus one half-gray launch that covers both views and all images, plus one upsample launch -- six to eight; never part of a plan. */
+int64_t mh_sgm_ws_bytes_scaled(int32_t B, int32_t H, int32_t W, int32_t D, int32_t paths, int32_t median, int32_t scale);
+int mh_sgm_proxy_scaled(const void* left, const void* right, int32_t frames_u8, void* ws, float* proxy,
+                        int32_t B, int32_t H, int32_t W, int32_t D, int32_t p1, int32_t p2, int32_t uniq, int32_t lr_tol,
+                        int32_t paths, int32_t median, int32_t scale, void* stream);
 /* Speckle filter of a finished label map, the last stage of an SGM pipeline (additive: the ABI version stays).  labels, out: [B][H][W] float32.
  *   Valid pixels: a pixel is valid when label > 0; NaN, 0 and negative labels are not.
  *   Connectivity: two pixels are connected when they are 4-neighbours inside the same frame (no row wrap, nothing from the next image of a batch), both are valid

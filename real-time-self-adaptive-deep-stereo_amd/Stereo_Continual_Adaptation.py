@@ -34,7 +34,25 @@ def d1_and_epe(disp, gt):
     return float(outliers.float().mean().item() * 100.), float(diff.mean().item())
 
 
+def check_proxy_args(args):
+    """the combinations of the --proxy* flags the matcher refuses, found before any device work"""
+    if getattr(args, 'proxyScale', 1) == 2 and args.proxyMaxDisp not in (128, 256, 384):
+        raise ValueError('--proxyMaxDisp %d: with --proxyScale 2 the legal values are 128, 256 and 384 (the half-size frames are searched over half of it)'
+                         % args.proxyMaxDisp)
+
+
+class _Parser(argparse.ArgumentParser):
+    def parse_args(self, *a, **k):
+        args = super().parse_args(*a, **k)
+        try:
+            check_proxy_args(args)
+        except ValueError as e:
+            self.error(str(e))
+        return args
+
+
 def main(args):
+    check_proxy_args(args)
     import torch
     from madnet_hip.adapter import Adapter
     with open(args.blockConfig) as json_data:
@@ -64,7 +82,7 @@ def main(args):
             # the proxy labels of every frame from the frame itself: census + semi-global matching on the prefetcher's upload stream (madnet_hip/proxy.py)
             from madnet_hip.proxy import ProxyMatcher
             matcher = ProxyMatcher(adapter.lib, 1, H, W, max_disp=args.proxyMaxDisp, device=dev, paths=args.proxyPaths, median=args.proxyMedian,
-                                   speckle_size=args.proxySpeckle, speckle_range=args.proxySpeckleRange)
+                                   speckle_size=args.proxySpeckle, speckle_range=args.proxySpeckleRange, scale=getattr(args, 'proxyScale', 1))
         frames = data_reader.device_prefetcher(data_set, dev, depth=3, consumer_stream=adapter.stream, cast=False, proxy_matcher=matcher)
         for left, right, gt, proxy, real_width in frames:
             out = adapter.step(left, right, gt[..., 0], proxy=proxy if matcher is not None else proxy[..., 0])
@@ -110,7 +128,7 @@ def main(args):
 
 
 def build_parser():
-    parser = argparse.ArgumentParser(description='Online adaptation of a deep stereo network on the MI355X engine')
+    parser = _Parser(description='Online adaptation of a deep stereo network on the MI355X engine')
     parser.add_argument("-l", "--list", help="CSV list of the frames to process (left,right,gt[,proxy] per row)", required=True)
     parser.add_argument("-o", "--output", help="folder that receives the reports (created if missing)", required=True)
     parser.add_argument("--weights", help="initial weights: TF checkpoint prefix, .npz of TF-named variables, xavier[:seed] or calibrated[:seed]", required=True)
@@ -134,7 +152,8 @@ def build_parser():
     parser.add_argument("--uf", help="gain of the reward added to the logits of the last trained portions", type=float, default=0.01)
     parser.add_argument("--precision", help="MFMA arithmetic of the conv kernels: fp32 (default; the reference adapts in fp32), mixed (forward within fp32 tolerance, bf16 gradients) or bf16 (opt-in throughput mode)", choices=['fp32', 'mixed', 'bf16'], default='fp32')
     parser.add_argument("--proxies", help="where the proxy labels come from: list = the fourth column of the list (disparity PNGs of an external matcher); sgm = computed on the GPU from every frame pair (census + four-path semi-global matching; --proxyPaths 8 adds the diagonal paths, --proxyMedian a 3x3 median of the labels, --proxySpeckle N a speckle filter), the list then needs only left,right,gt", choices=['list', 'sgm'], default='list')
-    parser.add_argument("--proxyMaxDisp", help="--proxies sgm: number of disparities searched (64, 128 or 192)", type=int, default=128)
+    parser.add_argument("--proxyMaxDisp", help="--proxies sgm: number of disparities searched at full resolution (64, 128 or 192; with --proxyScale 2: 128, 256 or 384, the half-size frames are searched over half of it)", type=int, default=128)
+    parser.add_argument("--proxyScale", help="--proxies sgm: 1 = match the frames as they are; 2 = match the half-size gray frames over --proxyMaxDisp / 2 disparities and write every label, doubled, to its 2 x 2 pixels (an eighth of the volume, about twice the mean label error, clearly worse on frames a few dozen rows high)", type=int, choices=[1, 2], default=1)
     parser.add_argument("--proxyPaths", help="--proxies sgm: aggregation paths, 4 = rows and columns, 8 = the four diagonals as well (fewer gross errors on full-size frames, worse on frames a few dozen rows high)", type=int, choices=[4, 8], default=4)
     parser.add_argument("--proxyMedian", help="--proxies sgm: 3x3 median of the valid labels", action='store_true')
     parser.add_argument("--proxySpeckle", help="--proxies sgm: speckle filter, labels in 4-connected components of at most N pixels are dropped (0 = off; removes a fifth of the labels on frames a few dozen rows high)", type=int, default=0)

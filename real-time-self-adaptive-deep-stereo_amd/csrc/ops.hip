@@ -1429,6 +1429,8 @@ extern "C" int mh_frame_prepare(const mh_frame_seg* segs, int32_t B, int32_t H, 
 // volumes into their sum S, uint16 [B][H][W][D] behind the volumes, which the right-view and select kernels read instead (the right-view walk gathers single
 // elements, and gathered from eight volumes it took 7.26 ms at 375 x 1242, D = 128, against 1.05 ms from four: profiles/sgm_proxy.txt); with the median the
 // labels before the filter, float [B][H][W], lie behind the right view's winners.
+// mh_sgm_proxy_scaled, scale 2: the same launches on the half grays [2][B][h][w] that sgm_half_gray_kernel writes in front of this workspace (the census then
+// reads a single channel: sgm_census_kernel<1>), and sgm_upsample2_kernel doubles the half-resolution labels behind it into `proxy`.
 #define SGM_BIG (1 << 20)
 #define SGM_CT_W 32             // census tile: 32 x 8 pixels per workgroup, halo 4 x 3
 #define SGM_CT_H 8
@@ -1449,7 +1451,9 @@ __device__ __forceinline__ int sgm_wave_min(int v) {
 }
 __device__ __forceinline__ int sgm_u8(float v) { return (int)fminf(fmaxf(floorf(v + 0.5f), 0.f), 255.f); }
 
-// gray + census 9 x 7 of both views: grid (tiles x, tiles y, 2 B), z = 2 b + view
+// gray + census 9 x 7 of both views: grid (tiles x, tiles y, 2 B), z = 2 b + view.  GRAY = 0: the sources are [B,H,W,3] frames, uint8 or float32 (a.u8);
+// GRAY = 1: they are [B,H,W] uint8 gray images (the half grays of mh_sgm_proxy_scaled) and are taken as they are
+template <int GRAY>
 __global__ __launch_bounds__(256) void sgm_census_kernel(SgmArgs a) {
     __shared__ int s_g[SGM_CT_H + 6][SGM_CT_W + 8];
     const int b = (int)blockIdx.z >> 1, view = (int)blockIdx.z & 1;
@@ -1459,6 +1463,7 @@ __global__ __launch_bounds__(256) void sgm_census_kernel(SgmArgs a) {
     for (int i = threadIdx.x; i < (SGM_CT_H + 6) * (SGM_CT_W + 8); i += 256) {
         const int ty = i / (SGM_CT_W + 8), tx = i - ty * (SGM_CT_W + 8);
         const int y = min(max(y0 + ty - 3, 0), a.H - 1), x = min(max(x0 + tx - 4, 0), a.W - 1);
+        if (GRAY) { s_g[ty][tx] = ((const unsigned char*)src)[frame + (int64_t)y * a.W + x]; continue; }
         const int64_t e = (frame + (int64_t)y * a.W + x) * 3;
         int r, g, bl;
         if (a.u8) {
@@ -1668,6 +1673,62 @@ __global__ __launch_bounds__(256) void sgm_median_kernel(const float* __restrict
     out[pix] = v[4] < __builtin_inff() ? r : 0.f;
 }
 
+// ---- mh_sgm_proxy_scaled, scale 2: the half grays in front of the matcher, the doubled labels behind it ----------------------------------------------------------------
+// the matcher's gray of one full-resolution pixel (as sgm_census_kernel<0> computes it); e = the index of its first channel
+__device__ __forceinline__ int sgm_gray_px(const void* __restrict__ src, int u8, int64_t e) {
+    int r, g, bl;
+    if (u8) {
+        const unsigned char* q = (const unsigned char*)src + e;
+        r = q[0]; g = q[1]; bl = q[2];
+    } else {
+        const float* q = (const float*)src + e;
+        r = sgm_u8(q[0]); g = sgm_u8(q[1]); bl = sgm_u8(q[2]);
+    }
+    return (77 * r + 150 * g + 29 * bl + 128) >> 8;
+}
+
+// g2 [2][B][h][w] (uint8) = the rounded 2 x 2 mean of the gray frame, both views and all images in one launch: grid (cdiv(h w, 256), 2 B), y = 2 b + view, one
+// thread per half pixel in row-major order.  Neighbouring lanes read neighbouring 6-byte (uint8) or 24-byte (float32) pieces of two source rows and store
+// neighbouring bytes; the last column of an odd W and the last row of an odd H read their own pixel twice.
+__global__ __launch_bounds__(256) void sgm_half_gray_kernel(const void* __restrict__ left, const void* __restrict__ right, unsigned char* __restrict__ g2,
+                                                            int B, int H, int W, int h, int w, int u8) {
+    const int p = (int)blockIdx.x * 256 + (int)threadIdx.x;
+    if (p >= h * w) return;
+    const int b = (int)blockIdx.y >> 1, view = (int)blockIdx.y & 1;
+    const void* src = view ? right : left;
+    const int y = p / w, x = p - y * w;
+    const int xa = 2 * x, xb = min(2 * x + 1, W - 1), ya = 2 * y, yb = min(2 * y + 1, H - 1);
+    const int64_t ra = ((int64_t)b * H + ya) * W, rb = ((int64_t)b * H + yb) * W;
+    const int s = sgm_gray_px(src, u8, (ra + xa) * 3) + sgm_gray_px(src, u8, (ra + xb) * 3) + sgm_gray_px(src, u8, (rb + xa) * 3) + sgm_gray_px(src, u8, (rb + xb) * 3);
+    g2[((int64_t)view * B + b) * h * w + p] = (unsigned char)((s + 2) >> 2);
+}
+
+__device__ __forceinline__ float sgm_up2(float l) { return l > 0.f ? 2.f * l : 0.f; }
+
+// proxy(b, y, x) = 2 l(b, y >> 1, x >> 1) where that label is > 0, else 0: grid (cdiv(W / 4 + 2, 64), cdiv(H, 4), B), 64 pieces x 4 rows per workgroup.  A row of
+// `proxy` starts anywhere (odd W, a caller's offset), so piece 0 is the `lead` floats in front of the row's first 16-byte boundary, written one by one, piece q >= 1
+// the four floats behind them at lead + 4 (q - 1), one 16-byte store, and the piece the row's end cuts is written one by one again.  A piece that starts at an odd
+// column takes three half labels, else two; the last row of an odd H reads row h - 1 like every other: y >> 1.
+__global__ __launch_bounds__(256) void sgm_upsample2_kernel(const float* __restrict__ lab, float* __restrict__ proxy, int H, int W, int h, int w) {
+    const int q = (int)blockIdx.x * 64 + ((int)threadIdx.x & 63), y = (int)blockIdx.y * 4 + ((int)threadIdx.x >> 6), b = (int)blockIdx.z;
+    if (y >= H) return;
+    float* __restrict__ row = proxy + ((int64_t)b * H + y) * W;
+    const float* __restrict__ src = lab + ((int64_t)b * h + (y >> 1)) * w;
+    const int lead = (int)((4u - (unsigned)(((uintptr_t)row >> 2) & 3u)) & 3u);
+    if (q == 0) {
+        for (int x = 0; x < min(lead, W); ++x) row[x] = sgm_up2(src[x >> 1]);
+        return;
+    }
+    const int64_t c64 = (int64_t)lead + 4 * (int64_t)(q - 1);
+    if (c64 >= W) return;
+    const int c = (int)c64;
+    if (c + 4 <= W) {
+        *reinterpret_cast<float4*>(row + c) = make_float4(sgm_up2(src[c >> 1]), sgm_up2(src[(c + 1) >> 1]), sgm_up2(src[(c + 2) >> 1]), sgm_up2(src[(c + 3) >> 1]));
+    } else {
+        for (int x = c; x < W; ++x) row[x] = sgm_up2(src[x >> 1]);
+    }
+}
+
 static inline int64_t sgm_align16(int64_t n) { return (n + 15) / 16 * 16; }
 
 extern "C" int64_t mh_sgm_ws_bytes_ex(int32_t B, int32_t H, int32_t W, int32_t D, int32_t paths, int32_t median) {
@@ -1679,11 +1740,13 @@ extern "C" int64_t mh_sgm_ws_bytes_ex(int32_t B, int32_t H, int32_t W, int32_t D
 
 extern "C" int64_t mh_sgm_ws_bytes(int32_t B, int32_t H, int32_t W, int32_t D) { return mh_sgm_ws_bytes_ex(B, H, W, D, 4, 0); }
 
-// census, aggregation, right view, select of one call: K = D / 64 disparities per lane, P paths
+// census, aggregation, right view, select of one call: K = D / 64 disparities per lane, P paths; gray: the sources are [B,H,W] uint8 gray images
 template <int K, int P>
-static int sgm_launch(const SgmArgs& a, hipStream_t s) {
+static int sgm_launch(const SgmArgs& a, bool gray, hipStream_t s) {
     const int64_t npix = a.npix;
-    hipLaunchKernelGGL(sgm_census_kernel, dim3((unsigned)mh_cdiv(a.W, SGM_CT_W), (unsigned)mh_cdiv(a.H, SGM_CT_H), (unsigned)(2 * a.B)), dim3(256), 0, s, a);
+    const dim3 cgrid((unsigned)mh_cdiv(a.W, SGM_CT_W), (unsigned)mh_cdiv(a.H, SGM_CT_H), (unsigned)(2 * a.B));
+    if (gray) hipLaunchKernelGGL(sgm_census_kernel<1>, cgrid, dim3(256), 0, s, a);
+    else hipLaunchKernelGGL(sgm_census_kernel<0>, cgrid, dim3(256), 0, s, a);
     if (int e = mh_check_launch("sgm_census")) return e;
     const int nlines = 2 * a.H + 2 * a.W + (P == 8 ? 4 * (a.H + a.W - 1) : 0);
     hipLaunchKernelGGL((sgm_paths_kernel<K, P>), dim3((unsigned)nlines, (unsigned)a.B), dim3(64), 0, s, a);
@@ -1700,9 +1763,10 @@ static int sgm_launch(const SgmArgs& a, hipStream_t s) {
     return mh_check_launch("sgm_select");
 }
 
-// the one host function behind both entries; `who` names the entry in the messages
-static int sgm_proxy_impl(const char* who, const void* left, const void* right, int32_t frames_u8, void* ws, float* proxy, int32_t B, int32_t H, int32_t W, int32_t D,
-                          int32_t p1, int32_t p2, int32_t uniq, int32_t lr_tol, int32_t paths, int32_t median, void* stream) {
+// the argument checks of every entry, nothing launched; `who` names the entry in the messages.  left / right / ws / proxy, H, W, D: what the matcher itself is given
+// (at scale 2 the half grays, the half frame, D / 2)
+static int sgm_check(const char* who, const void* left, const void* right, const void* ws, const float* proxy, int32_t B, int32_t H, int32_t W, int32_t D,
+                     int32_t p1, int32_t p2, int32_t uniq, int32_t lr_tol, int32_t paths, int32_t median) {
     MH_REQUIRE(left && right && ws && proxy, MH_ERR_ARG, "%s: null argument", who);
     MH_REQUIRE(B > 0 && H > 0 && W > 0, MH_ERR_ARG, "%s: bad dimension", who);
     MH_REQUIRE(H >= 7 && W >= 9, MH_ERR_ARG, "%s: the frame must hold one census window (H >= 7, W >= 9)", who);
@@ -1715,6 +1779,12 @@ static int sgm_proxy_impl(const char* who, const void* left, const void* right, 
     MH_REQUIRE(median == 0 || median == 1, MH_ERR_ARG, "%s: median must be 0 or 1", who);
     MH_REQUIRE(mh_aligned16(ws), MH_ERR_ALIGN, "%s: ws must be 16-byte aligned", who);
     MH_REQUIRE((int64_t)B * H * W < (1ll << 31) - 256 && B < 32768 && H < 65536 * SGM_CT_H, MH_ERR_UNSUPPORTED, "%s: too many pixels or frames", who);
+    return MH_OK;
+}
+
+// the matcher's launches on checked arguments.  gray: left, right are [B,H,W] uint8 gray images
+static int sgm_run(const void* left, const void* right, int32_t frames_u8, bool gray, void* ws, float* proxy, int32_t B, int32_t H, int32_t W, int32_t D,
+                   int32_t p1, int32_t p2, int32_t uniq, int32_t lr_tol, int32_t paths, int32_t median, void* stream) {
     SgmArgs a{};
     const int64_t npix = (int64_t)B * H * W;
     a.left = left; a.right = right;
@@ -1729,16 +1799,23 @@ static int sgm_proxy_impl(const char* who, const void* left, const void* right, 
     hipStream_t s = (hipStream_t)stream;
     int e;
     switch (D / 64 * 16 + paths) {
-        case 16 + 4: e = sgm_launch<1, 4>(a, s); break;
-        case 32 + 4: e = sgm_launch<2, 4>(a, s); break;
-        case 48 + 4: e = sgm_launch<3, 4>(a, s); break;
-        case 16 + 8: e = sgm_launch<1, 8>(a, s); break;
-        case 32 + 8: e = sgm_launch<2, 8>(a, s); break;
-        default: e = sgm_launch<3, 8>(a, s); break;
+        case 16 + 4: e = sgm_launch<1, 4>(a, gray, s); break;
+        case 32 + 4: e = sgm_launch<2, 4>(a, gray, s); break;
+        case 48 + 4: e = sgm_launch<3, 4>(a, gray, s); break;
+        case 16 + 8: e = sgm_launch<1, 8>(a, gray, s); break;
+        case 32 + 8: e = sgm_launch<2, 8>(a, gray, s); break;
+        default: e = sgm_launch<3, 8>(a, gray, s); break;
     }
     if (e || !median) return e;
     hipLaunchKernelGGL(sgm_median_kernel, dim3((unsigned)mh_cdiv(npix, 256)), dim3(256), 0, s, (const float*)raw, proxy, H, W, (int)npix);
     return mh_check_launch("sgm_median");
+}
+
+// the one host function behind the full-resolution entries
+static int sgm_proxy_impl(const char* who, const void* left, const void* right, int32_t frames_u8, void* ws, float* proxy, int32_t B, int32_t H, int32_t W, int32_t D,
+                          int32_t p1, int32_t p2, int32_t uniq, int32_t lr_tol, int32_t paths, int32_t median, void* stream) {
+    if (int e = sgm_check(who, left, right, ws, proxy, B, H, W, D, p1, p2, uniq, lr_tol, paths, median)) return e;
+    return sgm_run(left, right, frames_u8, false, ws, proxy, B, H, W, D, p1, p2, uniq, lr_tol, paths, median, stream);
 }
 
 extern "C" int mh_sgm_proxy_ex(const void* left, const void* right, int32_t frames_u8, void* ws, float* proxy, int32_t B, int32_t H, int32_t W, int32_t D,
@@ -1749,6 +1826,41 @@ extern "C" int mh_sgm_proxy_ex(const void* left, const void* right, int32_t fram
 extern "C" int mh_sgm_proxy(const void* left, const void* right, int32_t frames_u8, void* ws, float* proxy, int32_t B, int32_t H, int32_t W, int32_t D,
                             int32_t p1, int32_t p2, int32_t uniq, int32_t lr_tol, void* stream) {
     return sgm_proxy_impl("mh_sgm_proxy", left, right, frames_u8, ws, proxy, B, H, W, D, p1, p2, uniq, lr_tol, 4, 0, stream);
+}
+
+// scale 1: mh_sgm_ws_bytes_ex; scale 2 (D = the full-resolution range): half grays | the matcher's workspace on the half frame | half-resolution labels
+extern "C" int64_t mh_sgm_ws_bytes_scaled(int32_t B, int32_t H, int32_t W, int32_t D, int32_t paths, int32_t median, int32_t scale) {
+    if (scale == 1) return mh_sgm_ws_bytes_ex(B, H, W, D, paths, median);
+    if (scale != 2 || B <= 0 || H < 13 || W < 17 || (D != 128 && D != 256 && D != 384)) return 0;
+    const int32_t h = (H + 1) / 2, w = (W + 1) / 2;
+    const int64_t inner = mh_sgm_ws_bytes_ex(B, h, w, D / 2, paths, median), npix2 = (int64_t)B * h * w;
+    return inner ? sgm_align16(2 * npix2) + inner + sgm_align16(npix2 * 4) : 0;
+}
+
+extern "C" int mh_sgm_proxy_scaled(const void* left, const void* right, int32_t frames_u8, void* ws, float* proxy, int32_t B, int32_t H, int32_t W, int32_t D,
+                                   int32_t p1, int32_t p2, int32_t uniq, int32_t lr_tol, int32_t paths, int32_t median, int32_t scale, void* stream) {
+    const char* who = "mh_sgm_proxy_scaled";
+    MH_REQUIRE(scale == 1 || scale == 2, MH_ERR_ARG, "%s: scale must be 1 or 2", who);
+    MH_REQUIRE(B > 0 && H > 0 && W > 0, MH_ERR_ARG, "%s: bad dimension", who);
+    if (scale == 1) {
+        MH_REQUIRE(D == 64 || D == 128 || D == 192, MH_ERR_ARG, "%s: at scale 1 D must be 64, 128 or 192", who);
+        return sgm_proxy_impl(who, left, right, frames_u8, ws, proxy, B, H, W, D, p1, p2, uniq, lr_tol, paths, median, stream);
+    }
+    MH_REQUIRE(D == 128 || D == 256 || D == 384, MH_ERR_ARG, "%s: at scale 2 D is the full-resolution range and must be 128, 256 or 384", who);
+    MH_REQUIRE(H >= 13 && W >= 17, MH_ERR_ARG, "%s: at scale 2 the half frame must hold one census window (H >= 13, W >= 17)", who);
+    MH_REQUIRE(H <= 4 * 65535, MH_ERR_UNSUPPORTED, "%s: too many rows", who);
+    const int32_t h = (H + 1) / 2, w = (W + 1) / 2;
+    if (int e = sgm_check(who, left, right, ws, proxy, B, h, w, D / 2, p1, p2, uniq, lr_tol, paths, median)) return e;
+    const int64_t npix2 = (int64_t)B * h * w;
+    unsigned char* g2 = (unsigned char*)ws;                            // [2][B][h][w]
+    unsigned char* inner = g2 + sgm_align16(2 * npix2);               // the matcher's own workspace on the half frame
+    float* half = (float*)(inner + mh_sgm_ws_bytes_ex(B, h, w, D / 2, paths, median));      // the half-resolution labels [B][h][w]
+    hipStream_t s = (hipStream_t)stream;
+    hipLaunchKernelGGL(sgm_half_gray_kernel, dim3((unsigned)mh_cdiv((int64_t)h * w, 256), (unsigned)(2 * B)), dim3(256), 0, s, left, right, g2, B, H, W, h, w, frames_u8 ? 1 : 0);
+    if (int e = mh_check_launch("sgm_half_gray")) return e;
+    if (int e = sgm_run(g2, g2 + npix2, 1, true, inner, half, B, h, w, D / 2, p1, p2, uniq, lr_tol, paths, median, stream)) return e;
+    hipLaunchKernelGGL(sgm_upsample2_kernel, dim3((unsigned)mh_cdiv(W / 4 + 2, 64), (unsigned)mh_cdiv(H, 4), (unsigned)B), dim3(256), 0, s, (const float*)half, proxy, H, W, h, w);
+    return mh_check_launch("sgm_upsample2");
 }
 
 // ---- speckle filter of a finished label map (mh_sgm_speckle): 4-connected components of the valid labels, the small ones set to 0 ------------------------------------

@@ -820,22 +820,23 @@ def proxy_loss(lib, pred, proxy, ws, result, dpred=None, weight=0.01, grad_scale
     lib.proxy_loss(_p(pred), _p(proxy), _p(ws), _p(result), _p(dpred), weight, grad_scale, B, H, W, _p(stream))
 
 
-def sgm_proxy_ws(lib, B, H, W, D, device, paths=4, median=False):
-    """the workspace of sgm_proxy (census words, `paths` path volumes, the right view's winners, with the median the unfiltered labels): torch allocations are at
-    least 16-byte aligned"""
-    return torch.empty(int(lib.sgm_ws_bytes_ex(B, H, W, D, int(paths), int(bool(median)))), dtype=torch.uint8, device=device)
+def sgm_proxy_ws(lib, B, H, W, D, device, paths=4, median=False, scale=1):
+    """the workspace of sgm_proxy (census words, `paths` path volumes, the right view's winners, with the median the unfiltered labels; at scale 2 the half grays in
+    front and the half-resolution labels behind those of the half frame): torch allocations are at least 16-byte aligned.  D is the full-resolution range."""
+    return torch.empty(int(lib.sgm_ws_bytes_scaled(B, H, W, D, int(paths), int(bool(median)), int(scale))), dtype=torch.uint8, device=device)
 
 
-def sgm_proxy(lib, left, right, ws, out, max_disp=128, p1=10, p2=120, uniq=95, lr_tol=1, stream=None, paths=4, median=False):
-    """left, right [B,H,W,3] uint8 or float32 (0..255) -> out [B,H,W] float32 proxy disparities, 0 = rejected (mh_sgm_proxy_ex).  paths: 4 (rows and columns) or
-    8 (the diagonals as well); median: a 3x3 median of the valid labels.  Called directly, never recorded."""
+def sgm_proxy(lib, left, right, ws, out, max_disp=128, p1=10, p2=120, uniq=95, lr_tol=1, stream=None, paths=4, median=False, scale=1):
+    """left, right [B,H,W,3] uint8 or float32 (0..255) -> out [B,H,W] float32 proxy disparities, 0 = rejected (mh_sgm_proxy_scaled).  paths: 4 (rows and columns) or
+    8 (the diagonals as well); median: a 3x3 median of the valid labels; scale: 1, or 2 = match the half-size gray frames over max_disp / 2 disparities and write
+    every label, doubled, to its 2 x 2 pixels (max_disp stays the full-resolution range: 128, 256 or 384).  Called directly, never recorded."""
     B, H, W, c = left.shape
     assert c == 3 and right.shape == left.shape and right.dtype == left.dtype and left.dtype in (torch.uint8, torch.float32), "sgm_proxy: [B,H,W,3] uint8 or float32"
     assert left.is_contiguous() and right.is_contiguous() and out.is_contiguous() and out.dtype == torch.float32 and out.numel() == B * H * W
-    paths, median = int(paths), int(bool(median))
-    assert ws.numel() * ws.element_size() >= lib.sgm_ws_bytes_ex(B, H, W, int(max_disp), paths, median), "sgm_proxy: workspace too small"
-    lib.sgm_proxy_ex(_p(left), _p(right), int(left.dtype == torch.uint8), _p(ws), _p(out), B, H, W, int(max_disp), int(p1), int(p2), int(uniq), int(lr_tol),
-                     paths, median, _p(stream))
+    paths, median, scale = int(paths), int(bool(median)), int(scale)
+    assert ws.numel() * ws.element_size() >= lib.sgm_ws_bytes_scaled(B, H, W, int(max_disp), paths, median, scale), "sgm_proxy: workspace too small"
+    lib.sgm_proxy_scaled(_p(left), _p(right), int(left.dtype == torch.uint8), _p(ws), _p(out), B, H, W, int(max_disp), int(p1), int(p2), int(uniq), int(lr_tol),
+                         paths, median, scale, _p(stream))
     return out
 
 
