@@ -525,7 +525,8 @@ int mh_conv2d_head(const mh_conv_desc* d, const float* in, const float* w, const
  *        [kind 1] src0[pixel * src0_ld] + src1[pixel * src1_ld]   (either may be NULL)
  *   -> dV (fp32, [B,H,W]) and, if dV_shadow != NULL, its bf16 shadow (pixel stride 32 halfs, channel 0);
  *   dx (+)= conv2d_backprop_input(dV, w) * leaky'(mask_ref)  ([B,H,W,N], pixel stride dx_ld) and, if dx_shadow != NULL, its bf16 shadow
- *   (pixel stride round_up(N, 32)).  Replaces mh_resize_bwd / mh_copy_channels + mh_conv2d(mode 1, K = 1) of the reference's per-level
+ *   (pixel stride round_up(N, 32)).  With accumulate_dx the leaky mask applies to (gradient + old dx), not to the gradient alone: the store contract
+ *   of mh_conv2d (mode 1, accumulate).  Replaces mh_resize_bwd / mh_copy_channels + mh_conv2d(mode 1, K = 1) of the reference's per-level
  *   gradient chain. */
 typedef struct mh_head_bwd_desc {
     int32_t kind;                       /* 0 | 1 */

@@ -745,7 +745,8 @@ def head_bwd(lib, w, dV, dx, mask_ref=None, mask_alpha=1.0, accumulate_dx=False,
              dx_shadow=None, stream=None):
     """Backward front end of a disparity head (mh_head_bwd): dV [B,H,W] tensor <- either the resize gradient of the finer level's coordinate
     gradient `du` ([B,Ho,Wo] tensor; Hr, Wr, mul as resize_bwd mode 0) or the sum of up to two `addends` (Views with C = 1: channel slices are
-    fine); dx (View [B,H,W,N]) (+)= conv2d_backprop_input(dV, w) * leaky'(mask_ref).  w: HWIO [3,3,N,1] of the head conv.  Shadows: ops.Shadow of
+    fine); dx (View [B,H,W,N]) (+)= conv2d_backprop_input(dV, w) * leaky'(mask_ref).  With accumulate_dx the mask applies to the SUM: dx = (gradient +
+    old dx) * leaky'(mask_ref), the convention of mh_conv2d (mode 1, accumulate).  w: HWIO [3,3,N,1] of the head conv.  Shadows: ops.Shadow of
     dV (C = 1) / dx, written on the way."""
     B, H, W = dV.shape
     assert tuple(w.shape) == (3, 3, dx.C, 1) and (dx.B, dx.H, dx.W) == (B, H, W)

@@ -13,6 +13,11 @@ def _rand(shape, seed, dev, scale=1.0):
     return (torch.randn(*shape, generator=g) * scale).to(dev)
 
 
+def _urand(shape, seed, dev):
+    """uniform [0, 1) from a CPU generator with a literal seed: both backends see the same data"""
+    return torch.rand(*shape, generator=torch.Generator().manual_seed(seed)).to(dev)
+
+
 def _close(a, b, rtol=2e-5, atol=2e-6):
     a, b = a.detach().cpu(), b.detach().cpu()
     err = (a - b).abs().max().item()
@@ -596,9 +601,9 @@ def test_corr_warp_bwd_fused_matches_corr_bwd_then_warp_bwd(backend, case, form)
     dev = backend.device
     D = 2 * md // stride + 1
     ld = (Cc + D + 1 + 3) // 4 * 4
-    g = torch.randn(B, H, W, ld, device=dev)
-    L = torch.randn(B, H, W, Cc, device=dev); R = torch.randn(B, H, W, Cc, device=dev)
-    u = (torch.rand(B, H, W, device=dev) - 0.5) * 6.0
+    g = _rand((B, H, W, ld), 501, dev)
+    L = _rand((B, H, W, Cc), 502, dev); R = _rand((B, H, W, Cc), 503, dev)
+    u = (_urand((B, H, W), 504, dev) - 0.5) * 6.0
     if W >= 100:
         u = u * 20.0                      # taps far from their pixel, many of them clamped / masked at the row ends
     Rw = torch.zeros(B, H, W, Cc, device=dev)
@@ -646,13 +651,13 @@ def test_corr_warp_bwd_many_taps_on_one_column(backend):
     dev = backend.device
     D = 2 * md + 1
     ld = (Cc + D + 1 + 3) // 4 * 4
-    g = torch.randn(B, H, W, ld, device=dev)
-    L = torch.randn(B, H, W, Cc, device=dev); R = torch.randn(B, H, W, Cc, device=dev)
+    g = _rand((B, H, W, ld), 511, dev)
+    L = _rand((B, H, W, Cc), 512, dev); R = _rand((B, H, W, Cc), 513, dev)
     xs = torch.arange(W, dtype=torch.float32)
     u = torch.zeros(B, H, W)
     u[0, 0] = 17.3 - xs                                  # the whole row lands on columns 17 / 18
     u[0, 1, 10:22] = 5.5 - xs[10:22]                     # twelve pixels on columns 5 / 6, the rest in place
-    u[0, 2] = (torch.rand(W) - 0.5) * 3.0
+    u[0, 2] = (_urand((W,), 514, "cpu") - 0.5) * 3.0
     u = u.to(dev)
     Rw = torch.zeros(B, H, W, Cc, device=dev)
     ops.warp_fwd(backend.lib, ops.view(R), u, ops.view(Rw))
@@ -683,9 +688,9 @@ def test_corr_warp_bwd_row_form_is_deterministic_without_a_twin(backend):
     dev = backend.device
     D = 2 * md + 1
     ld = (Cc + D + 1 + 3) // 4 * 4
-    g = torch.randn(B, H, W, ld, device=dev)
-    L = torch.randn(B, H, W, Cc, device=dev); R = torch.randn(B, H, W, Cc, device=dev)
-    u = (torch.rand(B, H, W, device=dev) - 0.5) * 9.0
+    g = _rand((B, H, W, ld), 521, dev)
+    L = _rand((B, H, W, Cc), 522, dev); R = _rand((B, H, W, Cc), 523, dev)
+    u = (_urand((B, H, W), 524, dev) - 0.5) * 9.0
     Rw = torch.zeros(B, H, W, Cc, device=dev)
     ops.warp_fwd(backend.lib, ops.view(R), u, ops.view(Rw))
     gv = ops.View(g, B, H, W, ld, ld)
@@ -754,11 +759,11 @@ def test_head_bwd_matches_the_separate_launches(backend, case, kind):
     (same arithmetic, same order), bf16 shadows of both written on the way."""
     B, H, W, N = case
     dev = backend.device
-    w = torch.randn(3, 3, N, 1, device=dev) * 0.3
-    mref = torch.randn(B, H, W, N + 4, device=dev)
+    w = _rand((3, 3, N, 1), 531, dev, 0.3)
+    mref = _rand((B, H, W, N + 4), 532, dev)
     mv = ops.View(mref, B, H, W, N, N + 4)
-    old = torch.randn(B, H, W, N, device=dev)
-    V = torch.randn(B, H, W, device=dev)
+    old = _rand((B, H, W, N), 533, dev)
+    V = _rand((B, H, W), 534, dev)
     outs = []
     for fused in (False, True):
         dV = torch.full((B, H, W), float("nan"), device=dev)
@@ -767,15 +772,13 @@ def test_head_bwd_matches_the_separate_launches(backend, case, kind):
         dxv = ops.View(dxb, B, H, W, N, N + 4)
         shV, shx = ops.Shadow(B, H, W, 1, dev), ops.Shadow(B, H, W, N, dev)
         if kind == "du":
-            du = torch.randn(B, 2 * H, 2 * W, device=dev)
-            torch.manual_seed(5); du = torch.randn(B, 2 * H, 2 * W, device=dev)
+            du = _rand((B, 2 * H, 2 * W), 535, dev)
             if fused:
                 ops.head_bwd(backend.lib, w, dV, dxv, mask_ref=mv, mask_alpha=0.2, accumulate_dx=True, du=du, Hr=2 * H, Wr=2 * W, mul=2.5, dV_shadow=shV, dx_shadow=shx)
             else:
                 ops.resize_bwd(backend.lib, du, V, dV, 2 * H, 2 * W, mul=2.5, mode=0, accumulate=False)
         else:
-            torch.manual_seed(6)
-            a1 = torch.randn(B, H, W, device=dev); a2b = torch.randn(B, H, W, 8, device=dev)
+            a1 = _rand((B, H, W), 536, dev); a2b = _rand((B, H, W, 8), 537, dev)
             a2 = ops.View(a2b, B, H, W, 8, 8).slice(5, 6)
             if fused:
                 ops.head_bwd(backend.lib, w, dV, dxv, mask_ref=mv, mask_alpha=0.2, accumulate_dx=True, addends=(ops.view(a1), a2), dV_shadow=shV, dx_shadow=shx)
