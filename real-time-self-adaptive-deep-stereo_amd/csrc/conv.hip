@@ -930,7 +930,9 @@ static bool conv_thin_ok(const ConvArgs& a) {
     // step), which only amortises for the 2-step image layer.  The default therefore takes Cin <= 4 forward layers only;
     // mh_tune_conv_thin(n > 0) lifts the restriction for tests / experiments.
     const bool wide_ok = g_thin_min_m != 16384;
-    return g_thin_min_m >= 0 && a.bf16 && a.vecA && a.kh == 3 && a.kw == 3 && a.dil == 1 && g_pow2 && (a.N == 16 || a.N == 32) &&
+    // the kernel zeroes the lanes behind the last channel for ONE 4-channel group (Cin <= 3); a ragged Cin in several groups has no instance
+    const bool k_ok = a.G == 1 || a.K % 4 == 0;
+    return g_thin_min_m >= 0 && a.bf16 && a.vecA && a.kh == 3 && a.kw == 3 && a.dil == 1 && g_pow2 && k_ok && (a.N == 16 || a.N == 32) &&
            ((a.mode == 0 && a.stride <= 2) || (a.mode == 1 && a.stride == 1)) && a.M >= g_thin_min_m &&
            (wide_ok || (a.G == 1 && a.mode == 0));
 }

@@ -819,6 +819,7 @@ static int launch_wgrad_n1(WgradArgs& a, hipStream_t s) {
     if (a.query) return 0;
     const size_t lds = (size_t)slots * 9 * a.K * sizeof(float);          // <= 36 KiB
     if (t_capture) { t_capture->cfg = MH_WG_CFG_N1; t_capture->nblocks = a.splits; t_capture->lds = lds; return 0; }
+    mh_note_kernel("wgrad_n1_kernel<9> K=%d splits %d grid %d lds %d", a.K, a.splits, a.splits, (int)lds);
     hipLaunchKernelGGL(wgrad_n1_kernel<9>, dim3(a.splits), dim3(256), lds, s, a);
     return mh_check_launch("wgrad_n1");
 }

@@ -1,6 +1,6 @@
 """Store-footprint helpers of the op-level tests (no tests here): buffers with guard zones on both sides, prefilled with a NaN bit
 pattern, and checks on BITS -- so a kernel that stores a value equal to what was there, or stores outside the elements it owns, does not
-hide.  Used by test_conv_footprint.py, test_workspace_guards.py and test_shape_sweep.py."""
+hide.  Used by test_conv_footprint.py, test_workspace_guards.py and the test_*_sweep.py files."""
 import torch
 
 from madnet_hip import ops
@@ -14,6 +14,19 @@ _FILL = {4: NAN32, 2: NAN16, 1: 0xA5, 8: 0x7FF8BEEF7FC0BEEF}
 
 def round_up(n, m):
     return (n + m - 1) // m * m
+
+
+def bf16_round(t):
+    """the values a bf16 kernel sees: rounded to bf16, in the tensor's own type"""
+    return t.to(torch.bfloat16).to(t.dtype)
+
+
+def wide_rows(x, ld, dev, fill=float("nan")):
+    """[B,H,W,C] -> the same values in rows of ld floats on the device, `fill` (NaN: it must never reach a result) in the channel padding"""
+    B, H, W, Cc = x.shape
+    buf = torch.full((B, H, W, ld), fill)
+    buf[..., :Cc] = x
+    return buf.to(dev)
 
 
 def bits(t):
