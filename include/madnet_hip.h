@@ -485,6 +485,41 @@ int64_t mh_sgm_speckle_ws_bytes(int32_t B, int32_t H, int32_t W);
 int mh_sgm_speckle(const float* labels, float* out, void* ws, int32_t B, int32_t H, int32_t W,
                    int32_t max_size, float max_diff, void* stream);
 
+/* ---- preprocessing.colorize_img (preprocessing.py:91-117 of the reference) fused with the float -> uint8 normalisation TF 1.12's image summary applies to the
+ *      result before it encodes the PNG (summary_image_op.cc, NormalizeFloatImage).  Additive: the ABI version stays.  value: [B][H][W] float32.
+ *   Colour maps.  cmap 0 = `gray`, the reference's default: LUT[i] = (g, g, g), g = the float32 quotient (float) i / 255.0f.  cmap 1 = `jet`: matplotlib's
+ *      256-entry jet, matplotlib.colormaps['jet'](np.arange(256))[:, :3] cast to float32, a literal table in csrc/colorize_lut.h.  It is the piecewise-linear map
+ *      through these (x, y) points, evaluated in float64 at x_i = i / 255 and then cast: red (0, 0) (.35, 0) (.66, 1) (.89, 1) (1, .5); green (0, 0) (.125, 0)
+ *      (.375, 1) (.64, 1) (.91, 0) (1, 0); blue (0, .5) (.11, 1) (.34, 1) (.65, 0) (1, 0).  On the segment [xa, xb] that holds x_i (the first with xb * 255 >= 255 x_i):
+ *      y = (255 x_i - 255 xa) / (255 xb - 255 xa) * (yb - ya) + ya; entry 0 is the first y, entry 255 the last.  Both tables are >= 0; jet[0] = (0, 0, .5),
+ *      jet[255] = (.5, 0, 0); every entry's largest channel is >= .5.
+ *   1. Range.  use_range == 0: vmin / vmax = the smallest / largest FINITE element of the whole [B][H][W] tensor (tf.reduce_min spans the batch); otherwise the
+ *      arguments.  n = (v - vmin) / (vmax - vmin): one float32 subtraction in each place, one correctly rounded float32 division.  t = rintf(n * 255.0f), round
+ *      half to even as tf.round; idx = 255 where t >= 255, (int) t where 0 < t < 255, else 0.
+ *      Where the reference is undefined (it gathers out of range or divides by zero) the behaviour is OURS: (a) vmax == vmin gives idx = 0 everywhere; (b) a
+ *      non-finite v (NaN, +Inf, -Inf) is a BAD PIXEL: it takes no part in the range and gets the bad colour below; (c) an index outside 0 .. 255 under an explicit
+ *      range is clamped as stated, and a t that is NaN (possible only when a difference overflows float32) gives idx = 0.
+ *   2. out_kind 0, the API function: out = float32 [B][H][W][3] = LUT[cmap][idx]; a bad pixel is (1, 0, 0).
+ *   3. out_kind 1, the summary image: only image 0 of the batch is written (max_outputs = 1), out = uint8 [H][W][3], nothing behind H * W * 3 bytes is touched
+ *      (the range of step 1 still spans the batch).  image_max = the largest channel value of LUT[idx] over the pixels of image 0 that are not bad (0 when all are
+ *      bad); scale = image_max < 1e-6f ? 0 : 255.0f / image_max (float32); out = (uint8) (LUT[idx][c] * scale), one float32 product, truncated.  A bad pixel
+ *      is (255, 0, 0), TF's bad_color.  The scale is per image: a map that holds only its two extremes gives jet (0, 0, .5) and (.5, 0, 0), written as 255, not 127.
+ *      TF's branch for a negative minimum (127 / max, offset 128) cannot occur, both tables being >= 0, and is not built.
+ *   Every step is one IEEE float32 operation or a table read, min and max do not depend on their order, there are no atomics: the result is a function of the
+ *   input alone, two calls give the same bits.  Every element of `out` is written.
+ *   ws: mh_colorize_ws_bytes bytes (0 for a non-positive dimension), 16-byte aligned, each part rounded up to 16 bytes, with nq(n) = min(1024, ceil(n / 1024)):
+ *      partial (min, max) pairs [nq(B H W)][2] (float32) | partial image maxima [nq(H W)] (float32) | out_kind 1: the codes of image 0 [H][W] (uint16: idx, 256 =
+ *      bad pixel).  The size does not depend on out_kind.  The caller does not initialise it, the op never reads what it has not written in the same call, and
+ *      no byte behind the stated size is touched.
+ *   MH_ERR_ARG: a null pointer, a non-positive dimension, cmap other than 0 / 1, out_kind other than 0 / 1, use_range != 0 with a non-finite vmin or vmax.
+ *   MH_ERR_ALIGN: ws not 16-byte aligned.  MH_ERR_UNSUPPORTED: B * H * W >= 2^31 - 1024.  On a violation nothing is launched.  value and out need no alignment (16-byte
+ *      aligned value, 16- / 4-byte aligned out take the vector path).
+ *   Launches on `stream`: colorize_minmax_kernel (skipped when use_range != 0), then out_kind 0: colorize_float_kernel; out_kind 1: colorize_index_kernel and
+ *   colorize_apply_kernel -- one to three; never part of a plan. */
+int64_t mh_colorize_ws_bytes(int32_t B, int32_t H, int32_t W);
+int mh_colorize(const float* value, void* out, void* ws, int32_t B, int32_t H, int32_t W,
+                int32_t cmap, int32_t out_kind, int32_t use_range, float vmin, float vmax, void* stream);
+
 /* ---- preprocessing.pad_image (REFLECT, preprocessing.py:7-29) fused with the float cast
  *      and the channel padding 3 -> out_ld (extra channels zero) ------------------------ */
 /* out = in / div - sub  (MADNet: div=1, sub=0; DispNet._preprocess_inputs, DispNet.py:59-73: x/255 - 100/255) */

@@ -3,8 +3,8 @@ only), backed by the HIP kernels: pad_image, bilinear_sampler (general form) / w
 resize_to_prediction -- same names, argument meaning and autograd behaviour (gradients flow to the sampled coordinates / the
 disparity and to the images; tf.floor contributes none).  random_crop / augment (preprocessing.py:31-89) take the decoded 8-bit
 frames as device tensors and run on the kernel the training input runs on (mh_frame_prepare); their host statement, which
-that kernel is checked against, lives in Data_utils/data_reader.py.  Colour mapping (colorize_img) is outside the hot path and
-not provided."""
+that kernel is checked against, lives in Data_utils/data_reader.py.  colorize_img (preprocessing.py:91-117) maps a disparity through matplotlib's `gray`
+or `jet` table on the device (mh_colorize)."""
 import numpy as np
 import torch
 
@@ -104,6 +104,27 @@ def warp_image(img, flow):
     ys = torch.arange(H, dtype=torch.float32, device=flow.device).view(1, H, 1, 1).expand(B, H, W, 1)
     coords = torch.cat([xs - flow, ys], dim=-1)
     return bilinear_sampler(img, coords)
+
+
+def colorize_img(value, vmin=None, vmax=None, cmap=None):
+    """preprocessing.colorize_img (preprocessing.py:91-117): value [B,H,W,1] -> float32 [B,H,W,3] on value's device, the 256-entry colour map read at
+    round((value - vmin) / (vmax - vmin) * 255).  vmin / vmax default to the range of the whole tensor; cmap: None / 'gray' (the default) or 'jet', the two maps
+    the kernel holds.  Where the reference is undefined (vmax == vmin, non-finite values, indices outside 0..255) the result is mh_colorize's: index 0, the colour
+    (1, 0, 0), the clamped index."""
+    name = "gray" if cmap is None else cmap
+    if name not in ops.CMAPS:
+        raise ValueError("colorize_img: unknown colour map %r; the maps that exist are 'gray' and 'jet'" % (cmap,))
+    if (vmin is None) != (vmax is None):         # the reference takes the missing bound from the data
+        fin = value[torch.isfinite(value)]
+        vmin = float(fin.min()) if vmin is None else vmin
+        vmax = float(fin.max()) if vmax is None else vmax
+    B, H, W = value.shape[:3]
+    assert value.dim() == 4 and value.shape[3] == 1, "colorize_img: value is [B,H,W,1]"
+    v = value.reshape(B, H, W).contiguous().float()
+    out = torch.empty(B, H, W, 3, dtype=torch.float32, device=value.device)
+    lib = _lib()
+    ops.colorize(lib, v, out, ops.colorize_ws(lib, B, H, W, value.device), name, 0, vmin, vmax, stream=_stream(value))
+    return out
 
 
 def _as_u8(img):

@@ -2064,6 +2064,232 @@ extern "C" int mh_sgm_speckle(const float* labels, float* out, void* ws, int32_t
     return mh_check_launch("sgm_speckle_apply");
 }
 
+// ---- preprocessing.colorize_img + the uint8 normalisation of TF's image summary (mh_colorize; the definition is the header's) -------------------------------------
+// A few MB at the workload's size and launch-bound: a lane owns 4 consecutive pixels (one float4 in; 3 float4 or 3 dwords out), the colour map sits in LDS, and
+// the two reductions (range over the batch, image_max over image 0) are per-workgroup partials that EVERY workgroup of the next launch finishes, as
+// frame_apply_kernel finishes frame_sums_kernel's.  min / max are exact in any order, so capped grid-stride grids change no bit.
+#include "colorize_lut.h"
+#define CZ_MAX_PARTS 1024       // partials per reduction = workgroups of the launch that writes them
+#define CZ_BAD 256              // the code of a non-finite pixel
+
+struct ColorizeArgs {
+    const float* value; void* out; float* mm; float* imax; unsigned short* code;
+    int64_t n;                  // B * H * W
+    int npix0, nmm, nimax;      // H * W; partial counts
+    int cmap, use_range;
+    float vmin, vmax;
+};
+
+static inline int colorize_parts(int64_t n) { const int64_t w = (n + 1023) / 1024; return (int)(w < CZ_MAX_PARTS ? w : CZ_MAX_PARTS); }
+
+__device__ __forceinline__ bool colorize_finite(float v) { return fabsf(v) <= 3.402823466e+38f; }
+
+// min and max over the workgroup (256 lanes): wave shuffles, then one LDS slot per wave.  Every lane takes part and every lane gets the result.
+__device__ __forceinline__ void colorize_block_minmax(float& lo, float& hi, float (*red)[4]) {
+    for (int o = 32; o > 0; o >>= 1) { lo = fminf(lo, __shfl_xor(lo, o)); hi = fmaxf(hi, __shfl_xor(hi, o)); }
+    __syncthreads();                                    // (red may still be read from an earlier reduction)
+    if ((threadIdx.x & 63) == 0) { red[0][threadIdx.x >> 6] = lo; red[1][threadIdx.x >> 6] = hi; }
+    __syncthreads();
+    lo = fminf(fminf(red[0][0], red[0][1]), fminf(red[0][2], red[0][3]));
+    hi = fmaxf(fmaxf(red[1][0], red[1][1]), fmaxf(red[1][2], red[1][3]));
+}
+
+// four consecutive elements from q0 (q0 % 4 == 0, q0 < n); past the end: NaN, which no reduction counts and no store writes
+__device__ __forceinline__ void colorize_load4(const float* __restrict__ value, int64_t q0, int64_t n, float (&v)[4]) {
+    const float* p = value + q0;
+    if (q0 + 4 <= n && (((uintptr_t)p) & 15u) == 0) {
+        const float4 w = *reinterpret_cast<const float4*>(p);
+        v[0] = w.x; v[1] = w.y; v[2] = w.z; v[3] = w.w;
+    } else {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) v[j] = q0 + j < n ? p[j] : __builtin_nanf("");
+    }
+}
+
+// the colour map of this call in LDS: [256][3]
+__device__ __forceinline__ void colorize_fill_lut(float* lut, int cmap) {
+    for (int i = threadIdx.x; i < 768; i += 256) lut[i] = cmap ? MH_COLORIZE_JET[i / 3][i % 3] : (float)(i / 3) / 255.0f;
+}
+
+// step 1's range: the arguments, or the partial (min, max) pairs of colorize_minmax_kernel finished here
+__device__ __forceinline__ void colorize_range(const ColorizeArgs& a, float (*red)[4], float& vmin, float& vmax) {
+    if (a.use_range) { vmin = a.vmin; vmax = a.vmax; return; }
+    float lo = __builtin_inff(), hi = -__builtin_inff();
+    for (int i = threadIdx.x; i < a.nmm; i += 256) { lo = fminf(lo, a.mm[2 * i]); hi = fmaxf(hi, a.mm[2 * i + 1]); }
+    colorize_block_minmax(lo, hi, red);
+    vmin = lo; vmax = hi;
+}
+
+// idx of one value, or CZ_BAD
+__device__ __forceinline__ int colorize_code(float v, float vmin, float den, bool flat) {
+    MH_FP_EXACT
+    if (!colorize_finite(v)) return CZ_BAD;
+    if (flat) return 0;
+    const float n = (v - vmin) / den;
+    const float t = rintf(n * 255.0f);
+    return t >= 255.0f ? 255 : (t > 0.0f ? (int)t : 0);
+}
+
+// launch 1 (use_range == 0): workgroup i writes the (min, max) of the finite elements of its quads, (+Inf, -Inf) when it saw none
+__global__ __launch_bounds__(256) void colorize_minmax_kernel(ColorizeArgs a) {
+    __shared__ float red[2][4];
+    float lo = __builtin_inff(), hi = -__builtin_inff();
+    const int64_t nquad = (a.n + 3) >> 2;
+    for (int64_t q = (int64_t)blockIdx.x * 256 + threadIdx.x; q < nquad; q += (int64_t)gridDim.x * 256) {
+        float v[4];
+        colorize_load4(a.value, q * 4, a.n, v);
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+            if (colorize_finite(v[j])) { lo = fminf(lo, v[j]); hi = fmaxf(hi, v[j]); }
+    }
+    colorize_block_minmax(lo, hi, red);
+    if (threadIdx.x == 0) { a.mm[2 * blockIdx.x] = lo; a.mm[2 * blockIdx.x + 1] = hi; }
+}
+
+// out_kind 0: range, index, table read; a lane writes its 4 pixels as 3 float4
+__global__ __launch_bounds__(256) void colorize_float_kernel(ColorizeArgs a) {
+    __shared__ float red[2][4];
+    __shared__ float lut[768];
+    colorize_fill_lut(lut, a.cmap);
+    float vmin, vmax;
+    colorize_range(a, red, vmin, vmax);
+    __syncthreads();
+    const float den = vmax - vmin;
+    const bool flat = vmax == vmin;
+    const int64_t q0 = ((int64_t)blockIdx.x * 256 + threadIdx.x) * 4;
+    if (q0 >= a.n) return;
+    float v[4], c[12];
+    colorize_load4(a.value, q0, a.n, v);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        const int k = colorize_code(v[j], vmin, den, flat);
+        const bool bad = k == CZ_BAD;
+        const float* e = lut + 3 * (bad ? 0 : k);
+        c[3 * j] = bad ? 1.0f : e[0]; c[3 * j + 1] = bad ? 0.0f : e[1]; c[3 * j + 2] = bad ? 0.0f : e[2];
+    }
+    float* dst = (float*)a.out + q0 * 3;
+    if (q0 + 4 <= a.n && (((uintptr_t)dst) & 15u) == 0) {
+#pragma unroll
+        for (int k = 0; k < 3; ++k) reinterpret_cast<float4*>(dst)[k] = make_float4(c[4 * k], c[4 * k + 1], c[4 * k + 2], c[4 * k + 3]);
+    } else {
+#pragma unroll
+        for (int k = 0; k < 12; ++k) if (q0 + k / 3 < a.n) dst[k] = c[k];
+    }
+}
+
+// out_kind 1, first half: the codes of image 0 and, per workgroup, the largest channel of LUT[idx] over its pixels that are not bad (0 when it has none)
+__global__ __launch_bounds__(256) void colorize_index_kernel(ColorizeArgs a) {
+    __shared__ float red[2][4];
+    __shared__ float lut[768];
+    colorize_fill_lut(lut, a.cmap);
+    float vmin, vmax;
+    colorize_range(a, red, vmin, vmax);
+    __syncthreads();
+    const float den = vmax - vmin;
+    const bool flat = vmax == vmin;
+    float lo = 0.0f, hi = 0.0f;
+    const int nquad = (a.npix0 + 3) >> 2;
+    for (int q = (int)blockIdx.x * 256 + (int)threadIdx.x; q < nquad; q += (int)gridDim.x * 256) {
+        float v[4];
+        colorize_load4(a.value, (int64_t)q * 4, a.npix0, v);
+        unsigned k[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            k[j] = (unsigned)colorize_code(v[j], vmin, den, flat);
+            if (k[j] != CZ_BAD && q * 4 + j < a.npix0) hi = fmaxf(hi, fmaxf(fmaxf(lut[3 * k[j]], lut[3 * k[j] + 1]), lut[3 * k[j] + 2]));
+        }
+        unsigned short* dst = a.code + (int64_t)q * 4;                 // the code part starts 16-byte aligned: 8-byte aligned here
+        if (q * 4 + 4 <= a.npix0) {
+            *reinterpret_cast<uint2*>(dst) = make_uint2(k[0] | (k[1] << 16), k[2] | (k[3] << 16));
+        } else {
+#pragma unroll
+            for (int j = 0; j < 4; ++j) if (q * 4 + j < a.npix0) dst[j] = (unsigned short)k[j];
+        }
+    }
+    colorize_block_minmax(lo, hi, red);
+    if (threadIdx.x == 0) a.imax[blockIdx.x] = hi;
+}
+
+// out_kind 1, second half: image_max from the partials, then LUT[idx] * scale truncated to a byte.  Image 0 is a flat byte array: a lane's 4 pixels are 12 bytes =
+// three dword stores; the last H * W % 4 pixels (and everything, when out is not 4-byte aligned) go out bytewise.
+__global__ __launch_bounds__(256) void colorize_apply_kernel(ColorizeArgs a) {
+    MH_FP_EXACT
+    __shared__ float red[2][4];
+    __shared__ float lut[768];
+    colorize_fill_lut(lut, a.cmap);
+    float lo = 0.0f, hi = 0.0f;
+    for (int i = threadIdx.x; i < a.nimax; i += 256) hi = fmaxf(hi, a.imax[i]);
+    colorize_block_minmax(lo, hi, red);                 // (its barriers also publish lut)
+    const float scale = hi < 1e-6f ? 0.0f : 255.0f / hi;
+    const int p0 = ((int)blockIdx.x * 256 + (int)threadIdx.x) * 4;
+    if (p0 >= a.npix0) return;
+    const bool full = p0 + 4 <= a.npix0;
+    unsigned k[4] = {0u, 0u, 0u, 0u};
+    if (full) {
+        const uint2 w = *reinterpret_cast<const uint2*>(a.code + p0);
+        k[0] = w.x & 0xffffu; k[1] = w.x >> 16; k[2] = w.y & 0xffffu; k[3] = w.y >> 16;
+    } else {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) if (p0 + j < a.npix0) k[j] = a.code[p0 + j];
+    }
+    unsigned b[12];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        const bool bad = k[j] == CZ_BAD;
+        const float* e = lut + 3 * (bad ? 0u : k[j]);
+        b[3 * j] = bad ? 255u : (unsigned)(e[0] * scale); b[3 * j + 1] = bad ? 0u : (unsigned)(e[1] * scale); b[3 * j + 2] = bad ? 0u : (unsigned)(e[2] * scale);
+    }
+    unsigned char* dst = (unsigned char*)a.out + (int64_t)p0 * 3;
+    if (full && (((uintptr_t)dst) & 3u) == 0) {
+#pragma unroll
+        for (int w = 0; w < 3; ++w)
+            reinterpret_cast<unsigned*>(dst)[w] = (b[4 * w] & 0xffu) | ((b[4 * w + 1] & 0xffu) << 8) | ((b[4 * w + 2] & 0xffu) << 16) | (b[4 * w + 3] << 24);
+    } else {
+#pragma unroll
+        for (int i = 0; i < 12; ++i) if (p0 + i / 3 < a.npix0) dst[i] = (unsigned char)b[i];
+    }
+}
+
+extern "C" int64_t mh_colorize_ws_bytes(int32_t B, int32_t H, int32_t W) {
+    if (B <= 0 || H <= 0 || W <= 0) return 0;
+    const int64_t npix0 = (int64_t)H * W;
+    return sgm_align16((int64_t)colorize_parts(B * npix0) * 8) + sgm_align16((int64_t)colorize_parts(npix0) * 4) + sgm_align16(npix0 * 2);
+}
+
+extern "C" int mh_colorize(const float* value, void* out, void* ws, int32_t B, int32_t H, int32_t W, int32_t cmap, int32_t out_kind, int32_t use_range,
+                           float vmin, float vmax, void* stream) {
+    MH_REQUIRE(value && out && ws, MH_ERR_ARG, "mh_colorize: null argument");
+    MH_REQUIRE(B > 0 && H > 0 && W > 0, MH_ERR_ARG, "mh_colorize: bad dimension");
+    MH_REQUIRE(cmap == 0 || cmap == 1, MH_ERR_ARG, "mh_colorize: cmap must be 0 (gray) or 1 (jet)");
+    MH_REQUIRE(out_kind == 0 || out_kind == 1, MH_ERR_ARG, "mh_colorize: out_kind must be 0 (float32 [B,H,W,3]) or 1 (uint8 [H,W,3] of image 0)");
+    MH_REQUIRE(!use_range || (fabsf(vmin) < __builtin_inff() && fabsf(vmax) < __builtin_inff()), MH_ERR_ARG, "mh_colorize: vmin and vmax must be finite");
+    MH_REQUIRE(mh_aligned16(ws), MH_ERR_ALIGN, "mh_colorize: ws must be 16-byte aligned");
+    MH_REQUIRE((int64_t)B * H * W < (1ll << 31) - 1024, MH_ERR_UNSUPPORTED, "mh_colorize: too many pixels");
+    ColorizeArgs a{};
+    a.value = value; a.out = out;
+    a.npix0 = H * W; a.n = (int64_t)B * a.npix0;
+    a.nmm = colorize_parts(a.n); a.nimax = colorize_parts(a.npix0);
+    a.mm = (float*)ws;
+    a.imax = (float*)((char*)ws + sgm_align16((int64_t)a.nmm * 8));
+    a.code = (unsigned short*)((char*)a.imax + sgm_align16((int64_t)a.nimax * 4));
+    a.cmap = cmap; a.use_range = use_range ? 1 : 0; a.vmin = vmin; a.vmax = vmax;
+    hipStream_t s = (hipStream_t)stream;
+    if (!use_range) {
+        hipLaunchKernelGGL(colorize_minmax_kernel, dim3((unsigned)a.nmm), dim3(256), 0, s, a);
+        if (int e = mh_check_launch("colorize_minmax")) return e;
+    }
+    if (out_kind == 0) {
+        hipLaunchKernelGGL(colorize_float_kernel, dim3((unsigned)mh_cdiv(a.n, 1024)), dim3(256), 0, s, a);
+        mh_note_kernel("colorize_float_kernel grid %d, %d launch%s", mh_cdiv(a.n, 1024), use_range ? 1 : 2, use_range ? "" : "es");
+        return mh_check_launch("colorize_float");
+    }
+    hipLaunchKernelGGL(colorize_index_kernel, dim3((unsigned)a.nimax), dim3(256), 0, s, a);
+    if (int e = mh_check_launch("colorize_index")) return e;
+    hipLaunchKernelGGL(colorize_apply_kernel, dim3((unsigned)mh_cdiv(a.npix0, 1024)), dim3(256), 0, s, a);
+    mh_note_kernel("colorize_apply_kernel grid %d, %d launches", mh_cdiv(a.npix0, 1024), use_range ? 2 : 3);
+    return mh_check_launch("colorize_apply");
+}
+
 extern "C" int mh_resize_image_fwd(const float* in, float* out, int32_t B, int32_t Hi, int32_t Wi, int32_t C, int32_t Ho, int32_t Wo,
                                    void* stream) {
     MH_REQUIRE(in && out && B > 0 && Hi > 0 && Wi > 0 && C > 0 && Ho > 0 && Wo > 0, MH_ERR_ARG, "mh_resize_image_fwd: bad argument");

@@ -857,6 +857,30 @@ def sgm_speckle(lib, labels, out, ws, max_size, max_diff=1.0, stream=None):
     return out
 
 
+CMAPS = {"gray": 0, "jet": 1}          # the colour maps of mh_colorize, by matplotlib's names
+
+
+def colorize_ws(lib, B, H, W, device):
+    """the workspace of colorize (partial ranges, partial image maxima, the codes of image 0); torch allocations are at least 16-byte aligned"""
+    return torch.empty(int(lib.colorize_ws_bytes(B, H, W)), dtype=torch.uint8, device=device)
+
+
+def colorize(lib, value, out, ws, cmap, out_kind, vmin=None, vmax=None, stream=None):
+    """value [B,H,W] float32 through a colour map (mh_colorize): cmap 0 / 'gray' or 1 / 'jet'; out_kind 0: out = float32 [B,H,W,3], the reference's colorize_img;
+    out_kind 1: out = uint8 [H,W,3], image 0 as TF's image summary writes it.  vmin / vmax: both None = the range of the finite elements of the whole tensor,
+    otherwise both given.  Called directly, never recorded."""
+    assert value.dim() == 3 and value.dtype == torch.float32 and value.is_contiguous(), "colorize: [B,H,W] float32"
+    assert (vmin is None) == (vmax is None), "colorize: give both vmin and vmax or neither"
+    B, H, W = value.shape
+    cmap = CMAPS.get(cmap, cmap)
+    want = (torch.float32, B * H * W * 3) if int(out_kind) == 0 else (torch.uint8, H * W * 3)
+    assert out.is_contiguous() and out.device == value.device and (int(out_kind) not in (0, 1) or (out.dtype, out.numel()) == want), "colorize: wrong output tensor"
+    assert ws.numel() * ws.element_size() >= lib.colorize_ws_bytes(B, H, W), "colorize: workspace too small"
+    use = vmin is not None
+    lib.colorize(_p(value), _p(out), _p(ws), B, H, W, int(cmap), int(out_kind), int(use), float(vmin) if use else 0.0, float(vmax) if use else 0.0, _p(stream))
+    return out
+
+
 def proxy_loss_scaled(lib, pred, proxy, ws, result, scale, dpred=None, weight=0.1, grad_scale=1.0, stream=None):
     """proxy_loss of the prediction and the proxy labels both resized to (H // scale, W // scale), the labels divided by scale (a MAD block's loss under
     --reprojectionScale, Stereo_Continual_Adaptation.py:95-112) in one op; dpred = its gradient on the full-size grid (optional).  ws: proxy_scaled_ws_floats."""
