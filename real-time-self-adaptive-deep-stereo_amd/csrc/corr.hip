@@ -1595,6 +1595,7 @@ extern "C" int mh_corr_fwd_prec(const float* L, int32_t l_ld, const float* R, in
         if (C4 <= 4) hipLaunchKernelGGL((corr_fwd_small<4, 64>), grid, dim3(256), lds, s, a);
         else if (C4 <= 8) hipLaunchKernelGGL((corr_fwd_small<8, 64>), grid, dim3(256), lds, s, a);
         else hipLaunchKernelGGL((corr_fwd_small<16, 64>), grid, dim3(256), lds, s, a);
+        mh_note_kernel("corr_fwd_small<LPP=%d,TW=64>", C4 <= 4 ? 4 : (C4 <= 8 ? 8 : 16));
     } else if (g_corr_direct && stride == 1 && !copy_left && !u && !zero_tail && (C == 16 || C == 32 || C == 64 || C == 128 || C == 256) &&
                lb < (1ll << 31) - 64 && rb < (1ll << 31) - 64 &&
                (size_t)(48 + 16 * ((2 * max_disp + 31) / 16)) * (C + 4) * sizeof(float) <= 150 * 1024) {
@@ -1630,6 +1631,7 @@ extern "C" int mh_corr_fwd_prec(const float* L, int32_t l_ld, const float* R, in
         MH_REQUIRE(lds <= 150 * 1024, MH_ERR_UNSUPPORTED, "mh_corr_fwd: tiles do not fit LDS (C=%d, md=%d)", C, max_disp);
         // (the > 64 KiB dynamic-LDS opt-in of this kernel is done once in mh_init(), never during a capture)
         hipLaunchKernelGGL((corr_fwd_large<32>), dim3(a.segs * B * H), dim3(256), lds, s, a);
+        mh_note_kernel("corr_fwd_large<TW=32> C=%d D=%d", C, D);
     }
     return mh_check_launch("corr_fwd");
 }
@@ -1850,7 +1852,7 @@ extern "C" int mh_corr_bwd_prec(const float* g, int32_t g_ld, int32_t coff, cons
                 default: MH_CORRBH(16) break;
             }
 #undef MH_CORRBH
-            mh_note_kernel("corr_bwd_mfma_bf16_pair<C/16=%d> left + right in %s of %d x 4 waves, lds %d", C / 16, g_corr_pair.load() ? "one grid" : "two grids", (g_corr_pair.load() ? 2 : 1) * segs * B * H, (int)lds_r);
+            mh_note_kernel("corr_bwd_mfma_bf16_%s<C/16=%d> left + right in %s of %d x 4 waves, lds %d", g_corr_pair.load() ? "pair" : "one", C / 16, g_corr_pair.load() ? "one grid" : "two grids", (g_corr_pair.load() ? 2 : 1) * segs * B * H, (int)lds_r);
             return mh_check_launch("corr_bwd_mfma_bf16");
         }
     }

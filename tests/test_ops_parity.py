@@ -588,6 +588,14 @@ def test_corr_fwd_large_d_bf16_and_split_bf16(backend, case):
     assert (out1.cpu() - ref_bf).abs().max().item() <= 2e-6
     e2 = (out2.cpu() - ref).abs().max().item(); e1 = (out1.cpu() - ref).abs().max().item()
     assert e2 <= 5e-6 and e2 * 30 <= e1, (e1, e2)          # |corr| ~ 0.3: 2^-16 relative per product, averaged over C channels
+    # the three MFMA terms of the split in float64 (hi = bf16(x), lo = bf16(x - hi), mh_split_bf16x2): only the summation order is left, a dropped or
+    # doubled cross term -- ~1e-4 -- does not pass
+    Lc, Rc = L.cpu(), R.cpu()
+    (hl, ll), (hr, lr) = ((bf(t), bf(t - bf(t))) for t in (Lc, Rc))
+    c64 = lambda a, b: T.correlation(a.double(), b.double(), md, 1)
+    ref3 = c64(hl, hr) + c64(hl, lr) + c64(ll, hr)
+    e3 = (out2.cpu().double() - ref3).abs().max().item()
+    assert e3 <= 2e-6 * max(1.0, ref3.abs().max().item()), e3
 
 
 @pytest.mark.parametrize("form", ["rowlds", "row", "atomic"])
