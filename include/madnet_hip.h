@@ -95,6 +95,15 @@ int mh_conv2d(const mh_conv_desc* d, const float* in, const float* w, const floa
  * (the engines do it once per step, one launch for every layer).  Same arithmetic as the LDS-staged split-bf16 kernel. */
 int mh_conv2d_wb(const mh_conv_desc* d, const float* in, const float* w, const void* wb, const float* bias,
                  float* out, const float* mask_ref, void* stream);
+/* Pure query (nothing is launched), as if a correctly packed bank were offered: 1 if the launch described by d / these pointers would READ it -- the
+ * dispatch takes the small-layer bank kernel or a fragment-bank instance of the patch-staged kernel -- else 0 (any other kernel ignores wb).  Which bank
+ * a 1 asks for (mh_pack_seg planes, trans):  mode 0, precision 2: (2, 0), either bank kernel;  mode 0, precision 1: (1, 0), the small-layer kernel
+ * only;  mode 1, precision 1: (1, 1), the small-layer kernel only;  precision 0 and mode 1 / precision 2 never read a bank.  The engines pack a bank
+ * exactly where this says 1 (the plane kernels have queries of their own: mh_conv2d_planes_ok / mh_conv2d_planes_bwd_ok). */
+int mh_conv2d_takes_bank(const mh_conv_desc* d, const float* in, const float* w, float* out, const float* mask_ref);
+/* the small-layer bank kernel's limit in output pixels for a forward layer (input gradients: twice that; default 4096, mh_tune_conv_bank overrides):
+ * up to it a layer is latency bound -- the engines keep the plane kernels for the layers above it */
+int mh_conv_bank_small_maxpix(void);
 /* mh_conv2d_wb that ALSO writes out_shadow = bf16(out) as [pixel][N rounded up to 32] (round to nearest even, bit for bit the rounding of the
  * stored fp32 value; the padding channels [N, round_up(N, 32)) are not touched -- they keep whatever they held: allocate the shadow zeroed) -- the operand layout of mh_wgrad_stream, produced where the value is computed instead of by a
  * cast pass (+2 bytes per element written, nothing re-read).  wb and out_shadow may be NULL (then exactly mh_conv2d_wb / mh_conv2d). */

@@ -1160,7 +1160,7 @@ struct HeadOuts {
     float* out2 = nullptr; int out2_ld = 0; float* out3 = nullptr; int out3_ld = 0;      // mh_conv2d_head
     void* out_shadow = nullptr; void* out_lo = nullptr;                                  // bf16 shadow of the result (_sh*), its lo plane (_sh4)
     const void* in_shadow = nullptr; const void* mask_shadow = nullptr; int flags = 0;   // _sh2 / _sh3
-    int query = 0;                                                                       // mh_conv2d_takes_shadows: answer, launch nothing
+    int query = 0;                                                                       // answer, launch nothing: 1 = mh_conv2d_takes_shadows, 2 = mh_conv2d_takes_bank
 };
 int mh_plane_split_one(const float* src, int src_ld, int C, void* hi, void* lo, int dst_ld, int64_t npix, hipStream_t s);      // conv_planes.hip
 static int conv_entry(const mh_conv_desc* d, const float* in, const float* w, const void* wb, const float* bias,
@@ -1208,6 +1208,12 @@ extern "C" int mh_conv2d_takes_shadows(const mh_conv_desc* d, const float* in, c
     h.entry = "mh_conv2d_takes_shadows"; h.query = 1;
     return conv_entry(d, in, w, wb, nullptr, out, mask_ref, nullptr, h);
 }
+extern "C" int mh_conv2d_takes_bank(const mh_conv_desc* d, const float* in, const float* w, float* out, const float* mask_ref) {
+    alignas(16) static const char offered[16] = {};      // "as if a bank were offered": conv_entry only tests the pointer, a query reads nothing through it
+    HeadOuts h;
+    h.entry = "mh_conv2d_takes_bank"; h.query = 2;
+    return conv_entry(d, in, w, offered, nullptr, out, mask_ref, nullptr, h);
+}
 extern "C" int mh_conv2d_head(const mh_conv_desc* d, const float* in, const float* w, const float* bias, float* out,
                               float* out2, int32_t out2_ld, float* out3, int32_t out3_ld, void* stream) {
     MH_REQUIRE(d && d->N == 1 && d->mode == 0, MH_ERR_ARG, "mh_conv2d_head: a forward conv with ONE output channel");
@@ -1229,6 +1235,7 @@ struct ConvRoute {
     bool advertises;                              // whether mh_conv2d_takes_shadows reports it
     bool writes_shadow, writes_lo;                // epilogue stores; else the cast / split launch behind it
     bool maskless_stale_ok;                       // MH_CONV_MASK_F32_STALE on a launch without mask_ref: nothing to read, accepted (else any stale flag is refused)
+    bool reads_bank;                              // the launch streams its weights from the fragment bank wb (mh_conv2d_takes_bank)
 };
 static ConvRoute conv_route(const ConvArgs& a, const HeadOuts& h) {
     ConvRoute r{};
@@ -1241,7 +1248,8 @@ static ConvRoute conv_route(const ConvArgs& a, const HeadOuts& h) {
     r.advertises = true;
     switch (r.fam) {
     case N1: case THIN: break;
-    case K1_DGRAD: case BANK_SMALL: r.writes_shadow = true; break;
+    case K1_DGRAD: r.writes_shadow = true; break;
+    case BANK_SMALL: r.writes_shadow = r.reads_bank = true; break;
     case ROWS:
         r.writes_shadow = r.maskless_stale_ok = true;
         r.stages_in = r.reads_mask = in_sh && mask_sh;       // (the row kernel takes both or neither)
@@ -1251,6 +1259,7 @@ static ConvRoute conv_route(const ConvArgs& a, const HeadOuts& h) {
         r.writes_shadow = r.maskless_stale_ok = true;
         r.stages_in = in_sh; r.reads_mask = mask_sh;
         r.shadow_only = dgrad16 && (h.flags & MH_CONV_SHADOW_ONLY) && h.out_shadow && !a.accumulate;
+        r.reads_bank = mh_conv_patch_reads_bank(a);
         break;
     case TILED:
         r.writes_shadow = a.vecC != 0;         // the vector epilogue has the stores (hi and, where asked for, lo)
@@ -1356,6 +1365,7 @@ static int conv_entry(const mh_conv_desc* d, const float* in, const float* w, co
     a.shadow = nullptr; a.shadow_ld = (d->N + 31) / 32 * 32; a.shadow_done = 0;
     a.shadow_lo = nullptr; a.shadow_lo_done = 0;
     const ConvRoute r = conv_route(a, h);
+    if (h.query == 2) return r.reads_bank ? 1 : 0;
     if (h.query) return r.advertises && r.stages_in ? 1 | (r.reads_mask ? 2 : 0) : 0;        // (the mask bit is only ever reported with the input bit)
     if (h.out2 || h.out3) {
         MH_REQUIRE(r.fam == N1, MH_ERR_UNSUPPORTED, "mh_conv2d_head: the layer does not fit the single-output-channel kernel (Cin %% 4, aligned operands, <= 64 KB of weights)");

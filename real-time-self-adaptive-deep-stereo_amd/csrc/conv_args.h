@@ -49,6 +49,7 @@ static inline unsigned conv_shadow_bytes(int B, int H, int W, int C) {
 // conv_patch.hip: patch-staged bf16 kernel for the stride-1 3x3 (dilated) layers
 bool mh_conv_patch_ok(const ConvArgs& a);
 int mh_conv_patch_launch(ConvArgs& a, hipStream_t s);     // a.M < 0: attribute set-up only
+bool mh_conv_patch_reads_bank(const ConvArgs& a);         // a layer mh_conv_patch_ok takes: does its launch run a fragment-bank instance?
 extern "C" int mh_tune_conv_patch(int mode);
 // conv_patch.hip: fragment-bank kernel of the small layers (a.wb = the bank mh_pack_weights wrote for this mode / precision)
 bool mh_conv_bank_small_ok(const ConvArgs& a);

@@ -1215,7 +1215,7 @@ extern "C" int mh_pack_weights(const mh_pack_seg* segs_device, int32_t nseg, int
     hipLaunchKernelGGL(pack_weights_kernel, dim3(nblocks), dim3(256), 0, (hipStream_t)stream, segs_device, nseg);
     return mh_check_launch("pack_weights");
 }
-std::atomic<int> g_bank_small_maxpix{-2};          // -2: the default (4096; the engines' bank_small_maxpix must agree: they pack the banks for it)
+std::atomic<int> g_bank_small_maxpix{-2};          // -2: the default (4096); the engines ask (mh_conv2d_takes_bank, mh_conv_bank_small_maxpix)
 int bank_small_maxpix() {
     const int m = g_bank_small_maxpix.load(std::memory_order_relaxed);
     return m == -2 ? 4096 : m;
@@ -1225,6 +1225,7 @@ int bank_small_tile_wgs() {
     const int m = g_bank_small_tile_wgs.load(std::memory_order_relaxed);
     return m < 0 ? 200 : m;
 }
+extern "C" int mh_conv_bank_small_maxpix(void) { return bank_small_maxpix(); }
 extern "C" int mh_tune_conv_bank_small(int mode) { return g_bank_small_place.exchange(mode < 0 ? -1 : mode); }
 extern "C" int mh_tune_conv_bank_tile(int max_wgs) { return g_bank_small_tile_wgs.exchange(max_wgs < 0 ? -1 : max_wgs); }
 extern "C" int mh_tune_conv_bank(int small_maxpix) {
@@ -1294,6 +1295,9 @@ bool mh_conv_patch_ok(const ConvArgs& a) {
     return (int64_t)a.B * d * d * mh_cdiv(mh_cdiv(a.Ho, d), TH) * mh_cdiv(mh_cdiv(a.Wo, d), 16) < (1 << 30);
 }
 
+// the fragment-bank instances (split-bf16 forward) serve every column tile: a layer this family takes reads the bank it is given
+bool mh_conv_patch_reads_bank(const ConvArgs& a) { return a.wb && a.x3 && a.mode == 0 && !(patch_mode() & 0x4000); }      // mode bit 14: ignore the bank
+
 int mh_conv_patch_launch(ConvArgs& a, hipStream_t s) {
     const bool all = a.M < 0;
     const bool dg = a.mode == 1;
@@ -1302,7 +1306,7 @@ int mh_conv_patch_launch(ConvArgs& a, hipStream_t s) {
     int rc = 0;
     // fragment-bank instances (mh_conv2d_wb: the layer's weights packed by mh_pack_weights; split-bf16 forward)
     {
-        const bool wb = !all && a.wb && a.x3 && a.mode == 0 && !(patch_mode() & 0x4000);       // mode bit 14: ignore the bank
+        const bool wb = !all && mh_conv_patch_reads_bank(a);
         const bool big = !all && (patch_mode() & 0x8000) != 0;                                  // mode bit 15: 128-pixel tile (64x32 wave tiles)
         if (all || (wb && bn == 128 && big)) { rc = launch_bank<2, 4, 4, 2, true>(a, s); if (!all || rc) return rc; }
         const bool w4 = !all && (patch_mode() & 0x10000) != 0;                                 // mode bit 16: 64-pixel tile with 4 waves of 64x32 (half the fragment bytes per MFMA)

@@ -13,6 +13,7 @@ Memory layout (all float32, NHWC, resident in HBM for the life of the engine):
     correlation kernel (no tf.concat copies); channel counts are padded to multiples of 4 so all
     row accesses are 16-byte vectors.
 """
+import collections
 import ctypes as C
 import os
 
@@ -28,6 +29,11 @@ from .backward import BackwardRecorder
 from .netdef import PYR, EST, CTX, LEVELS, FEAT, ALPHA, _r4, pyr_name, est_name, ctx_name, _merge_ranges, madnet_manifest      # noqa: F401  (re-exported: E.LEVELS ...)
 
 
+# a 3x3 conv layer of the net: the Views its recorded launches use (forward x -> o; input gradient dz -> dx, dx None: the image layer), stride, dilation,
+# code = the precision code its forward pass runs, act = x is a leaky activation (its mask joins the input gradient), pyramid = its index there (0 elsewhere)
+Layer = collections.namedtuple("Layer", "name x o dx dz stride dil code act pyramid")
+
+
 class MadNetEngine(EngineBase, ElisionPasses, BackwardRecorder):
     def __init__(self, lib, H, W, B=1, device="cuda", radius_d=2, stride=1, warping=True, weights=None, precision="fp32", schedule=None):
         """precision: 'fp32' = exact fp32 MFMA (parity path, default) | 'bf16' = bf16 MFMA inputs with fp32
@@ -40,6 +46,7 @@ class MadNetEngine(EngineBase, ElisionPasses, BackwardRecorder):
         self.md, self.cstride = radius_d, stride
         self.D = 2 * radius_d // stride + 1
         self._alloc()
+        self.layers = {L.name: L for L in self._layer_table()}
         self._plans = {}
         self._zeros_needed = []
         # filter gradients: atomic-free split reduction (ops.conv2d_wgrad_partial) unless switched off
@@ -57,9 +64,8 @@ class MadNetEngine(EngineBase, ElisionPasses, BackwardRecorder):
         # split-bf16 3x3 layers of the 1/4- and 1/8-resolution estimators and the context network stream their weights from MFMA
         # fragment banks (mh_conv2d_wb), re-packed by ONE launch at the start of every step
         # ... and (bf16 / mixed) the layers of the 1/16-1/64 levels -- forward and input gradient -- take the small-layer bank kernel
+        # (which layers: _bank_plan, from the library's answers)
         self.use_bank = precision in ("mixed", "bf16") and os.environ.get("MH_CONV_BANK", "1") != "0"
-        self.bank_small_maxpix = 4096           # = the library default (mh_tune_conv_bank): the banks are packed for the layers that kernel takes
-        self.bank_min_n = 32
         self.banks = {}
         self.banks_d = {}
         # bf16 backward: the filter gradients of the stride-1 3x3 layers run on the streaming kernel (mh_wgrad_stream: one launch per batch,
@@ -203,67 +209,63 @@ class MadNetEngine(EngineBase, ElisionPasses, BackwardRecorder):
             return 1
         return fcode
 
+    def _layer_table(self):
+        """the net's 3x3 conv layers (Layer) in forward order, from netdef and the allocated buffers: what record_forward launches and _bank_plan asks the
+        library about.  Forward codes: the mode's, except ('mixed') plain bf16 for conv7 .. conv12 (_pyr_code) and the estimators of levels 6 .. 4."""
+        B, fv = self.B, self._fv
+        fcode = ops.PRECISION_CODES[self.precision][0]
+        out = []
+
+        def chain(names, x, dx, acts, grads, dils, codes, pyramid=False):
+            for j, name in enumerate(names):
+                s = PYR[j][2] if pyramid else 1
+                out.append(Layer(name, x, fv(acts[j]), dx, fv(grads[j]), s, dils[j], codes[j], j > 0, (j + 1) if pyramid else 0))
+                x, dx = fv(acts[j]), fv(grads[j])
+
+        ids = range(1, 13)
+        chain([pyr_name(i) for i in ids], ops.View(self.X0, 2 * B, self.Hp, self.Wp, 3, 4), None, [self.F[i] for i in ids], [self.dF[i] for i in ids],
+              [1] * 12, [self._pyr_code(i, fcode) for i in ids], pyramid=True)
+        for k in LEVELS:
+            h, w, c = self.fshape[FEAT[k]]
+            cin, ld = c + self.D + (0 if k == 6 else 1), self.dsi_ld[k]
+            chain([est_name(k, j) for j in range(1, 7)], ops.View(self.dsi[k], B, h, w, cin, ld), ops.View(self.ddsi[k], B, h, w, cin, ld),
+                  self.E[k] + [self.V[k]], self.dE[k] + [self.dV[k]], [1] * 6, [1 if (self.precision == "mixed" and k >= 4) else fcode] * 6)
+        h, w, c = self.fshape[4]
+        chain([ctx_name(j) for j in range(1, 8)], ops.View(self.ctx_in, B, h, w, c + 1, self.ctx_ld), ops.View(self.dctx_in, B, h, w, c + 1, self.ctx_ld),
+              self.Cx + [self.final], self.dCx + [self.dfinal], [rate for _, rate in CTX], [fcode] * 7)
+        return out
+
     def _bank_plan(self):
-        """[(layer, planes, trans)]: which fragment banks this engine packs every step.  Forward: planes follow the precision code the
-        layer runs (2 = split-bf16 -> the 64x128 / 128x64 bank kernel or, <= bank_small_maxpix output pixels, the small-layer kernel;
-        1 = bf16 -> small-layer kernel only).  Input gradient (trans 1, bf16): small layers."""
+        """[(layer, planes, trans)]: the fragment banks packed at the head of every step -- one wherever the library says the recorded launch reads it:
+        ops.conv2d_planes_ok / conv2d_planes_bwd_ok for the plane kernels (32x32x16 banks, trans 2 / 3), ops.conv2d_takes_bank for the bank kernels behind
+        mh_conv2d* (trans 0 / 1), each asked with the layer's own Views.  Every shape, size and instance condition is the library's.  What is decided HERE
+        is policy: the schedule's flags, the precision code a layer runs, and the priority between the families -- a plane kernel before a bank kernel, but
+        only on layers above the small-layer kernel's pixel limit (below it a layer is latency bound: that kernel or the tiled ones)."""
         if not self.use_bank:
             return []
-        fcode, bcode = ops.PRECISION_CODES[self.precision]
-        shapes = dict(self.params.manifest)
-        B = self.B
-        layers = []          # (name, forward precision code, output pixels)
-        stride2 = set()
-        s2_planes = []
-        for i in range(2, 13):                                      # the stride-1 pyramid layers and the small stride-2 ones (conv7 / 9 / 11)
-            h, w = (self.fshape[i][0], self.fshape[i][1])
-            if PYR[i - 1][2] == 2:
-                if 2 * B * h * w > self.bank_small_maxpix:
-                    # (round 6) the LARGE stride-2 layers named by Schedule.PLANES_S2_FWD run the stride-2 plane kernel (split-bf16 from their producer's planes)
-                    # instead of the exact-fp32 tiled kernel: a 32x32x16 bank, forward only
-                    if (i in self.sched.PLANES_S2_FWD and self.use_planes and fcode == 2 and self._pyr_code(i, fcode) == 2
-                            and ops.conv2d_planes_ok(self.lib, self._fv(self.F[i - 1]), self.W_(pyr_name(i)), 1, stride=2)):
-                        s2_planes.append(pyr_name(i))
-                    continue
-                stride2.add(pyr_name(i))
-            layers.append((pyr_name(i), self._pyr_code(i, fcode), 2 * B * h * w))
-        for k in LEVELS:
-            h, w, _ = self.fshape[FEAT[k]]
-            code = 1 if (self.precision == "mixed" and k >= 4) else fcode
-            layers += [(est_name(k, j), code, B * h * w) for j in range(1, 7)]
-        h, w, _ = self.fshape[4]
-        layers += [(ctx_name(j), fcode, B * h * w) for j in range(1, 8)]
-        plan = [(n, 2, 2) for n in s2_planes]
-        for n, code, pix in layers:
-            kh, _, K, N = shapes[n + "/weights"]
-            if kh != 3:
+        bcode = ops.PRECISION_CODES[self.precision][1]
+        plan = []
+        for L in self.layers.values():
+            w = self.W_(L.name)
+            large = L.o.npix > self.lib.conv_bank_small_maxpix()
+            # plane kernels: split-bf16 layers only (code 2 -- the library also has one-plane forward instances, which 'mixed' does not use); stride 2: the layers
+            # Schedule.PLANES_S2_FWD names
+            if (self.use_planes and L.code == 2 and large and (L.stride == 1 or L.pyramid in self.sched.PLANES_S2_FWD)
+                    and ops.conv2d_planes_ok(self.lib, L.x, w, L.dil, stride=L.stride)):
+                plan.append((L.name, 2, 2))
+            elif ops.conv2d_takes_bank(self.lib, L.x, w, L.o, L.stride, L.dil, 0, L.code):
+                plan.append((L.name, L.code, 0))
+            if bcode != 1 or L.dx is None:
                 continue
-            small = pix <= self.bank_small_maxpix and 9 * ((K + 31) // 32) <= 64
-            if code == 2 and not small and n not in stride2 and self._planes_layer(K, N):
-                plan.append((n, 2, 2))
-            elif code == 2 and N >= 16 and K >= 16 and (small or (N >= self.bank_min_n and K >= self.bank_min_n)):
-                plan.append((n, 2, 0))
-            elif code == 1 and small and N >= 16 and K >= 16:
-                plan.append((n, 1, 0))
-            if n in stride2:
-                continue                                            # (forward only: the stride-2 input gradient runs parity classes on the tiled kernel)
-            if bcode == 1 and pix > self.bank_small_maxpix and PYR[int(n.rsplit("conv", 1)[1]) - 1][2] == 1 if "pyramid" in n else (bcode == 1 and pix > self.bank_small_maxpix):
-                if self._planes_bwd_layer(K, N):
-                    plan.append((n, 1, 3))
-                    continue
-            if bcode == 1 and pix <= 2 * self.bank_small_maxpix and K >= 16 and N >= 16 and 9 * ((N + 31) // 32) <= 64:
-                plan.append((n, 1, 1))
-        # the LARGE stride-2 pyramid layers whose input gradient is the first contribution to its target (conv3: F2 feeds no cost volume): the parity-class
-        # plane kernel (mh_conv2d_planes_bwd on a stride-2 descriptor) from the one-plane mirrored / transposed bank
-        if bcode == 1 and self.use_planes and self.sched.PLANES_DGRAD:
-            for i in range(3, 13):
-                h, w = self.fshape[i][0], self.fshape[i][1]
-                # (round 6: the parity-class kernel accumulates, so a layer whose input is a cost-volume level -- conv5: F4 already holds the correlation's gradient -- qualifies)
-                if PYR[i - 1][2] == 2 and 2 * B * h * w > self.bank_small_maxpix and ((i - 1) not in FEAT.values() or self.sched.PLANES_S2_ACC):
-                    _, _, K, N = shapes[pyr_name(i) + "/weights"]
-                    dxv = self._fv(self.dF[i - 1])
-                    if ops.conv2d_planes_bwd_ok(self.lib, dxv, self.W_(pyr_name(i)), 1, stride=2):
-                        plan.append((pyr_name(i), 1, 3))
+            # input gradient (bf16).  The stride-2 plane kernel runs where it is the first contribution to its target (the layer's input feeds no cost volume) or,
+            # Schedule.PLANES_S2_ACC, adds onto the correlation's gradient; never on a layer whose input is a concat buffer (L.act: the first layer of an estimator /
+            # the context network, padded gradient rows) -- the library has instances for some of those, the step was never measured with them
+            first = L.stride == 1 or (L.pyramid - 1) not in FEAT.values() or self.sched.PLANES_S2_ACC
+            if (self.use_planes and self.sched.PLANES_DGRAD and large and first and L.act
+                    and ops.conv2d_planes_bwd_ok(self.lib, L.dx, w, L.dil, stride=L.stride)):
+                plan.append((L.name, 1, 3))
+            elif ops.conv2d_takes_bank(self.lib, L.dz, w, L.dx, L.stride, L.dil, 1, bcode, mask_ref=(L.x if L.act else None)):
+                plan.append((L.name, 1, 1))
         return plan
 
     def _stamp(self, lib, label):
@@ -273,17 +275,6 @@ class MadNetEngine(EngineBase, ElisionPasses, BackwardRecorder):
             self.stamps = torch.zeros(64, dtype=torch.int64, device=self.dev)
         self.stamp_labels.append((label, getattr(lib, "lane", 0)))
         ops.stamp(lib, self.stamps, len(self.stamp_labels) - 1)
-
-    def _planes_layer(self, K, N):
-        """does mh_conv2d_planes have an instance for a stride-1 3x3 layer with K input / N output channels?  (csrc/conv_planes.hip)"""
-        return self.use_planes and N % 8 == 0 and N <= 128 and ((K + 15) // 16) in (2, 3, 4, 5, 6, 8)
-
-    def _planes_bwd_layer(self, K, N):
-        """does mh_conv2d_planes_bwd have an instance for the input gradient of a stride-1 3x3 layer K -> N?"""
-        if not (self.use_planes and self.sched.PLANES_DGRAD):
-            return False
-        d = ops.conv_desc(1, 8, 8, 8, 8, K, N, 3, 3, 1, 1, 1, 1, 0, 0, K, 0, precision=1)
-        return self.lib.conv2d_planes_bwd_ok(C.byref(d)) == 1
 
     def _bank_of(self, trans):
         return {0: self.banks, 1: self.banks_d, 2: self.banks32, 3: self.banks32t}[trans]
@@ -296,8 +287,9 @@ class MadNetEngine(EngineBase, ElisionPasses, BackwardRecorder):
             self.images.mark(v, lo=True)        # the hi plane is the tensor's bf16 shadow: no cast in the backward pass
         return pl
 
-    def _conv_fwd(self, lib, r, x, base, o, stride=1, dil=1, alpha=ALPHA, precision=None, shadow_consumer=None):
-        """forward conv of layer `base`: from planes (mh_conv2d_planes) where the layer has a 32x32x16 bank, else the fp32-operand kernels"""
+    def _conv_fwd(self, lib, r, L, alpha=ALPHA, shadow_consumer=None):
+        """forward conv of Layer L: from planes (mh_conv2d_planes) where the layer has a 32x32x16 bank, else the fp32-operand kernels"""
+        x, base, o, stride, dil, precision = L.x, L.name, L.o, L.stride, L.dil, L.code
         wb32 = self.banks32.get(base)              # (stride 2: only the layers _bank_plan gave a 32x32x16 bank -- Schedule.PLANES_S2_FWD)
         if wb32 is not None:
             xp = self._in_planes(lib, x, r)
@@ -351,19 +343,16 @@ class MadNetEngine(EngineBase, ElisionPasses, BackwardRecorder):
                     ops.pad_reflect(lib, self.lr, self.X0, self.pt, self.pl)
         else:
             ops.pad_reflect(lib, self.lr, self.X0, self.pt, self.pl)
-        x = ops.View(self.X0, 2 * B, self.Hp, self.Wp, 3, 4)
-        for i, (ci, co, s) in enumerate(PYR, 1):
-            o = self._fv(self.F[i])
+        for i in range(1, 13):
+            L = self.layers[pyr_name(i)]
             if i == 1 and image_conv:
-                ops.conv_image_fwd(lib, self.lr, self.Hp, self.Wp, self.pt, self.pl, self.W_(pyr_name(1)), self.b_(pyr_name(1)), o, stride=s, alpha=ALPHA,
-                                   shadow=self._out_shadow(o, pyr_name(2)))
-                x = o
+                ops.conv_image_fwd(lib, self.lr, self.Hp, self.Wp, self.pt, self.pl, self.W_(L.name), self.b_(L.name), L.o, stride=L.stride, alpha=ALPHA,
+                                   shadow=self._out_shadow(L.o, pyr_name(2)))
                 continue
             if i == 2 and self.use_bank and self.sched.PACK_SIDE and hasattr(lib, "lane") and self.wgrad_lanes > 0:
                 lib.join_lanes_next = 1 << 1                  # conv1 (3 input channels) never has a bank: every later layer waits for the packing
             # F_i is the input of layer i + 1 (stride 1 or 2: both streamed)
-            self._conv_fwd(lib, r, x, pyr_name(i), o, stride=s, precision=self._pyr_code(i), shadow_consumer=(pyr_name(i + 1) if i < 12 else None))
-            x = o
+            self._conv_fwd(lib, r, L, shadow_consumer=(pyr_name(i + 1) if i < 12 else None))
         for k in LEVELS:
             f = FEAT[k]
             h, w, c = self.fshape[f]
@@ -401,15 +390,14 @@ class MadNetEngine(EngineBase, ElisionPasses, BackwardRecorder):
                     Rk = self._fv(self.Rw[k])
                 ops.corr_fwd(lib, Lk, Rk, dsi, self.md, self.cstride, coff=c, u=(None if k == 6 else self.u[k]),
                              copy_left=True, zero_tail=True)
-            x = ops.View(self.dsi[k], B, h, w, c + self.D + (0 if k == 6 else 1), ld)
-            # 'mixed': the estimators of the three coarsest levels run plain bf16 in the forward pass too -- measured
+            # 'mixed': the estimators of the three coarsest levels run plain bf16 in the forward pass too (_layer_table) -- measured
             # contribution to the final disparity 8e-6 / 1e-5 / 1.3e-4 px (profiles/r02_precision_map.txt: rounding ONE group's
             # operands to bf16, everything else fp32), against 2.7e-3 px for level 3 and 7e-2 px for level 2, which keep
             # split-bf16 / exact fp32 like the pyramid and the context network
-            fprec = 1 if (self.precision == "mixed" and k >= 4) else None
             for j, co in enumerate(EST):
                 last = j == len(EST) - 1
-                o = self._fv(self.V[k]) if last else self._fv(self.E[k][j])
+                L = self.layers[est_name(k, j + 1)]
+                x, o = L.x, L.o
                 if last and k == 2 and self.sched.FUSE_HEAD and hasattr(lib, "conv2d_head"):
                     # the level-2 head also fills the disparity slot of the context network's input and seeds final = V2 + context7 (two copy
                     # launches on the critical chain before)
@@ -417,16 +405,12 @@ class MadNetEngine(EngineBase, ElisionPasses, BackwardRecorder):
                     ops.conv2d_head(lib, x, self.W_(est_name(k, j + 1)), self.b_(est_name(k, j + 1)), o,
                                     copies=(ops.View(self.ctx_in, B, h4, w4, c4_ + 1, self.ctx_ld).slice(c4_, c4_ + 1), self._fv(self.final)))
                     head2_fused = True
-                    x = o
                     continue
                 if last and k != 2 and self._head_in_front(k, x):
                     # levels 6 .. 3: the head runs inside level k - 1's front-end launch, which needs its result first (Schedule.HEAD_IN_FRONT)
                     pending_head = (x, est_name(k, j + 1))
-                    x = o
                     continue
-                self._conv_fwd(lib, r, x, est_name(k, j + 1), o, alpha=(1.0 if last else ALPHA), precision=fprec,
-                               shadow_consumer=(None if last else est_name(k, j + 2)))
-                x = o
+                self._conv_fwd(lib, r, L, alpha=(1.0 if last else ALPHA), shadow_consumer=(None if last else est_name(k, j + 2)))
             if k != 2:
                 sc = 2 ** (k - 1)
                 if not self._front_fused():          # (fused: level k-1's front kernel computes u itself)
@@ -447,15 +431,12 @@ class MadNetEngine(EngineBase, ElisionPasses, BackwardRecorder):
             ops.copy_channels(lib, self._half(self.F[4], False), cin.slice(0, c))
             if not head2_fused:
                 ops.copy_channels(lib, self._fv(self.V[2]), cin.slice(c, c + 1))
-        x = cin
-        for j, (co, rate) in enumerate(CTX[:-1]):
-            o = self._fv(self.Cx[j])
-            self._conv_fwd(lib, r, x, ctx_name(j + 1), o, dil=rate, shadow_consumer=ctx_name(j + 2))
-            x = o
+        for j in range(1, len(CTX)):
+            self._conv_fwd(lib, r, self.layers[ctx_name(j)], shadow_consumer=ctx_name(j + 1))
         # final_disp = V2_init + context7  (accumulating epilogue)
         if not head2_fused:
             ops.copy_channels(lib, self._fv(self.V[2]), self._fv(self.final))
-        self._conv_acc(lib, x, ctx_name(7), self._fv(self.final), CTX[-1][1])
+        self._conv_acc(lib, self.layers[ctx_name(7)].x, ctx_name(7), self._fv(self.final), CTX[-1][1])
         if 2 in make_disps:
             self._make_disp(lib, self.final, self.disp_k[2])
         # rescaled_prediction: relu AFTER resize (MadNet.py:362-364)

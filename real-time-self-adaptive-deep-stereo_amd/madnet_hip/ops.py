@@ -109,17 +109,37 @@ def conv_geometry(H, W, kh, kw, stride, dil):
     return Ho, Wo, pt, pl
 
 
+def _fwd_desc(x, w, out, stride, dil, precision, **kw):
+    """descriptor of the forward conv x -> out (Views; w: HWIO); precision None = the recording's forward code"""
+    kh, kw_, cin, cout = w.shape
+    Ho, Wo, pt, pl = conv_geometry(x.H, x.W, kh, kw_, stride, dil)
+    assert (out.H, out.W, out.C) == (Ho, Wo, cout) and x.C == cin
+    return conv_desc(x.B, x.H, x.W, Ho, Wo, cin, cout, kh, kw_, stride, dil, pt, pl, 0, 0, x.ld, out.ld, precision=precision, **kw)
+
+
+def _dgrad_desc(dz, w, dx, stride, dil, precision, **kw):
+    """descriptor of the input gradient dz -> dx of that conv; precision None = the recording's backward code"""
+    kh, kw_, cin, cout = w.shape
+    Ho, Wo, pt, pl = conv_geometry(dx.H, dx.W, kh, kw_, stride, dil)
+    assert (dz.H, dz.W, dz.C) == (Ho, Wo, cout) and dx.C == cin
+    return conv_desc(dx.B, Ho, Wo, dx.H, dx.W, cout, cin, kh, kw_, stride, dil, pt, pl, 1, 1, dz.ld, dx.ld,
+                     precision=(_bwd_precision() if precision is None else precision), **kw)
+
+
+def conv2d_takes_bank(qlib, x, w, out, stride, dil, mode, precision, mask_ref=None):
+    """mh_conv2d_takes_bank (qlib = the real library): would conv2d_fwd (mode 0: x -> out) / conv2d_dgrad (mode 1: x = dz, out = dx) of this layer in
+    this precision code read a fragment bank if it were given one?"""
+    d = (_dgrad_desc if mode else _fwd_desc)(x, w, out, stride, dil, precision, mask_ld=(mask_ref.ld if mask_ref is not None else 0))
+    return qlib.conv2d_takes_bank(C.byref(d), _p(x), _p(w), _p(out), _p(mask_ref)) == 1
+
+
 def conv2d_fwd(lib, x, w, b, out, stride=1, dil=1, alpha=1.0, accumulate=False, mask_ref=None, mask_alpha=1.0,
                mask_range=(0, 0), stream=None, precision=None, wb=None, shadow=None, out_planes=None):
     """out (+)= leaky(conv2d_SAME(x, w) + b) [* leaky'(mask_ref)].  x,out: View; w: HWIO [kh,kw,Cin,Cout].
     wb: the layer's MFMA fragment bank (pack_weights) -- split-bf16 3x3 layers then stream their weights from it.
     out_planes: Planes of `out` (hi + lo) the launch writes too (mh_conv2d_sh4: the producer side of conv2d_planes)."""
-    kh, kw, cin, cout = w.shape
-    Ho, Wo, pt, pl = conv_geometry(x.H, x.W, kh, kw, stride, dil)
-    assert (out.H, out.W, out.C) == (Ho, Wo, cout) and x.C == cin
-    d = conv_desc(x.B, x.H, x.W, Ho, Wo, cin, cout, kh, kw, stride, dil, pt, pl, 0, 0, x.ld, out.ld, alpha=alpha,
-                  mask_ld=(mask_ref.ld if mask_ref is not None else 0), accumulate=int(accumulate), mask_alpha=mask_alpha,
-                  mask_c0=mask_range[0], mask_c1=mask_range[1], precision=precision)
+    d = _fwd_desc(x, w, out, stride, dil, precision, alpha=alpha, mask_ld=(mask_ref.ld if mask_ref is not None else 0), accumulate=int(accumulate),
+                  mask_alpha=mask_alpha, mask_c0=mask_range[0], mask_c1=mask_range[1])
     if out_planes is not None:
         assert (out_planes.B, out_planes.H, out_planes.W, out_planes.C) == (out.B, out.H, out.W, out.C)
         lib.conv2d_sh4(C.byref(d), _p(x), _p(w), _p(wb), _p(b), _p(out), _p(mask_ref), C.c_void_p(out_planes.hi.ptr), C.c_void_p(out_planes.lo.ptr), _p(stream))
@@ -197,12 +217,8 @@ def conv2d_dgrad(lib, dz, w, dx, stride=1, dil=1, accumulate=False, mask_ref=Non
                  stream=None, wb=None, shadow=None, dz_shadow=None, mask_shadow=None):
     """dx (+)= conv2d_backprop_input(dz, w); optionally fused dx *= leaky'(mask_ref).
     dz: View [B,Ho,Wo,Cout]; dx: View [B,H,W,Cin]; w: HWIO of the forward conv."""
-    kh, kw, cin, cout = w.shape
-    Ho, Wo, pt, pl = conv_geometry(dx.H, dx.W, kh, kw, stride, dil)
-    assert (dz.H, dz.W, dz.C) == (Ho, Wo, cout) and dx.C == cin
-    d = conv_desc(dx.B, Ho, Wo, dx.H, dx.W, cout, cin, kh, kw, stride, dil, pt, pl, 1, 1, dz.ld, dx.ld,
-                  mask_ld=(mask_ref.ld if mask_ref is not None else 0), accumulate=int(accumulate),
-                  alpha=1.0, mask_alpha=mask_alpha, mask_c0=mask_range[0], mask_c1=mask_range[1], precision=_bwd_precision())
+    d = _dgrad_desc(dz, w, dx, stride, dil, None, mask_ld=(mask_ref.ld if mask_ref is not None else 0), accumulate=int(accumulate),
+                    mask_alpha=mask_alpha, mask_c0=mask_range[0], mask_c1=mask_range[1])
     if dz_shadow is not None or mask_shadow is not None:
         # dz_shadow / mask_shadow: ops.Shadow of dz / of mask_ref that a producer already wrote: the patch-staged kernel stages the first instead of
         # converting dz and tests the sign of the second instead of reading the fp32 activation (other kernels ignore both)

@@ -84,7 +84,7 @@ class Schedule(object):
     # mh_corr_warp_bwd runs) accumulate into 64-bit fixed-point twins (mh_deterministic_add) that the plan flushes in front of their readers --
     # two replays of the same step give bit-identical weights.  At most four deterministic engines per process (two ranges each).
     DETERMINISTIC: bool = field(default_factory=lambda: os.environ.get("MH_DETERMINISTIC", "0") == "1")
-    # 'mixed': the split-bf16 forward layers (stride-1 3x3, > bank_small_maxpix pixels) run from PRE-SPLIT operands (mh_conv2d_planes):
+    # 'mixed': the split-bf16 forward layers (stride-1 3x3, above the small-layer bank kernel's pixel limit) run from PRE-SPLIT operands (mh_conv2d_planes):
     # activations as hi / lo bf16 planes -- hi is the shadow the backward pass reads anyway -- written by the producer's epilogue, staged by LDS DMA
     USE_PLANES: bool = field(default_factory=_env_flag("MH_CONV_PLANES", "1"))
     # ... and the fp32 copy of such an activation is not stored when no op of the plan reads it (elision.elide_fp32_activations)

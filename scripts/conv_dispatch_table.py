@@ -4,7 +4,7 @@ are the backend's own bits).
   (a) every kernel family at a small shape, forced with the tuning hooks, LAUNCHED: mode 0 / 1, precision 0 / 1 / 2, with bias, mask, sub-range mask,
       accumulation, an unaligned output, the lo plane (mh_conv2d_sh4).  One line per case: return code, mh_last_kernel(), query bits, for flags 2 / 4 / 6
       the return code with / without the shadows and whether the NaN-filled output was written, hash of the result and of its shadow
-  (b) the query alone at every OP_CONV descriptor of the recorded MADNet / DispNet FULL plans at 375x1242 and 320x1216, B = 1 and 4
+  (b) the queries alone (mh_conv2d_takes_shadows, mh_conv2d_takes_bank) at every OP_CONV descriptor of the recorded MADNet / DispNet FULL plans at 375x1242 and 320x1216, B = 1 and 4
 Only entry points of ABI 16.  usage: conv_dispatch_table.py [--lib PATH]   (default: the CPU emulator, tests/emul/libmadnet_emul.so; a product library
 runs on cuda:0)"""
 import ctypes as C
@@ -133,8 +133,9 @@ def queried(lib, dev):
                         d, f = oplayout.conv_desc(c), oplayout.fields(c)
                         ints = [getattr(d, name) for name, _ in d._fields_]
                         bits = q(C.byref(d), C.c_void_p(f.inp), C.c_void_p(f.w), C.c_void_p(f.wb), C.c_void_p(f.out), C.c_void_p(f.mask))
+                        reads = lib.conv2d_takes_bank(C.byref(d), C.c_void_p(f.inp), C.c_void_p(f.w), C.c_void_p(f.out), C.c_void_p(f.mask))
                         print("b", "%dx%d B=%d %s %s op %d" % (H, W, B, net, prec, k), " ".join(str(v) for v in ints), "bank=%d mask=%d" % (bool(f.wb), bool(f.mask)),
-                              "takes=%d" % bits)
+                              "takes=%d" % bits, "takes_bank=%d" % reads)
                     eng.close()
                     sys.stdout.flush()
 

@@ -1050,7 +1050,6 @@ def test_mixed_forward_from_planes_matches_fp32_operand_path(bname, mode):
             if planes == "unfused" and mode != "FULL":
                 continue
             eng = E.MadNetEngine(lib, 60, 100, B=1, device=dev, weights=wn, precision="mixed", schedule=E.Schedule(USE_PLANES=bool(planes), FUSE_SPLITS=(planes != "unfused")))
-            eng.bank_small_maxpix = 128
             eng.set_inputs(l, r, gt[..., 0])
             if mode == "FULL":
                 plan = eng.build_plan("FULL", lr=1e-3)
