@@ -421,6 +421,46 @@ int64_t mh_frame_prepare_ws_floats(int32_t B, int32_t H, int32_t W);
 int mh_frame_prepare(const mh_frame_seg* segs, int32_t B, int32_t H, int32_t W,
                      float* left, float* right, float* gt, float* ws, void* stream);
 
+/* ---- the live demo's input side: rectification of raw camera views on the device.  The reference leaves "all the op necessary to read/decode and rectify
+ *      stereo frames" to each Demo/grabber.py subclass (README.MD:97) and its one grabber lets the camera SDK do it; here two calls do it for any pair of
+ *      pinhole cameras from a calibration (additive: the ABI version stays).  Both run outside the captured step, like mh_frame_prepare: no allocation, no host
+ *      synchronisation, no atomics, every element of the output written -- two calls give the same bits.
+ *
+ *      mh_rectify_map: the documented formula of OpenCV's initUndistortRectifyMap.  map[i][v][u] = the raw-view position (x, y) that output pixel (u, v) of
+ *      view i shows, in float32, UN-contracted (no fused multiply-add), with every sum associated as written (fl = one float32 rounding per operation):
+ *         x   = ((float)u - cxn) / fxn                         y   = ((float)v - cyn) / fyn
+ *         X   = (R[0] x + R[3] y) + R[6]       Y = (R[1] x + R[4] y) + R[7]       W = (R[2] x + R[5] y) + R[8]            (the transpose of R times (x, y, 1))
+ *         x'  = X / W      y' = Y / W      xx = x' x'      yy = y' y'      xy = x' y'      r2 = xx + yy      r4 = r2 r2      r6 = r4 r2
+ *         rad = ((1 + k1 r2) + k2 r4) + k3 r6
+ *         x'' = (x' rad + (2 p1) xy) + p2 (r2 + 2 xx)
+ *         y'' = (y' rad + p1 (r2 + 2 yy)) + (2 p2) xy
+ *         map = (fx x'' + cx, fy y'' + cy)
+ *      Where W <= 0 (or is NaN) or a coordinate is not finite, map = (-2, -2): a position at which mh_remap samples nothing.  `cams` is host memory, read during
+ *      the call (the V records travel as kernel arguments).  One launch.
+ *
+ *      mh_remap: out[i][v][u][:] = the exact bilinear sample of view i of `src` at (mx, my) = map[i][v][u], constant border 0:
+ *         x0 = floor(mx), tx = mx - x0, y0 = floor(my), ty = my - y0                  (floor, not truncation: a coordinate in (-1, 0) still takes its inside tap)
+ *         out = (s00 (1 - tx) + s01 tx) (1 - ty) + (s10 (1 - tx) + s11 tx) ty          s_jk = src[y0 + j][x0 + k], 0 where that tap lies outside the source
+ *      in float32, un-contracted, associated as written.  The weights are the coordinate's own fraction: there are NO 1/32 fixed-point interpolation tables
+ *      (OpenCV's remap quantises the fraction to 5 bits; this does not), so an integer coordinate returns the source value exactly.  A coordinate outside
+ *      (-1, Ws) x (-1, Hs), or one that is not finite, gives 0.  Source channels: Cs = 3 as they are, Cs = 4 the first three, Cs = 1 replicated.  The output
+ *      stays on the source's scale (0..255 for 8-bit frames) and is not rounded.  Any map may be passed: one uploaded for another lens model works as well.
+ *      One launch.
+ *
+ *      MH_ERR_ARG, nothing launched: a null pointer, V outside 1..4, a non-positive size, Cs not 1, 3 or 4, a focal length (fx, fy, fxn, fyn) that is zero or
+ *      not finite, more than 2^31 source elements (V Hs Ws Cs).  MH_ERR_UNSUPPORTED: Ho * Wo * 3 >= 2^31.  map and out need no alignment (16-byte aligned
+ *      pointers take the vector path). */
+typedef struct mh_camera_model {
+    float fx, fy, cx, cy;          /* camera matrix of the raw view                       */
+    float k1, k2, p1, p2, k3;      /* distortion, OpenCV's order                          */
+    float R[9];                    /* rectifying rotation, row-major: x_rect = R x_cam    */
+    float fxn, fyn, cxn, cyn;      /* camera matrix of the rectified view (P[:, :3])      */
+} mh_camera_model;
+int mh_rectify_map(const mh_camera_model* cams /* host, read during the call */, int32_t V, int32_t Ho, int32_t Wo,
+                   float* map /* [V][Ho][Wo][2] = (x, y) in the raw view */, void* stream);
+int mh_remap(const void* src /* [V][Hs][Ws][Cs], uint8 if src_u8 else float32 */, int32_t src_u8, const float* map,
+             float* out /* [V][Ho][Wo][3] float32 */, int32_t V, int32_t Hs, int32_t Ws, int32_t Cs, int32_t Ho, int32_t Wo, void* stream);
+
 /* ---- proxy labels of the continual loop from an on-device matcher: replaces the proxy column of continual_data_reader (README.MD:59-61 of the reference:
  *      "proxy labels ... computed with a traditional stereo algorithm" offline, one 16-bit PNG per frame).  Census 9 x 7 on the gray frames
  *      (77 R + 150 G + 29 B + 128 >> 8, replicate border), Hamming cost for d = 0 .. D-1 (64 where x - d < 0), four-path semi-global aggregation (left->right,

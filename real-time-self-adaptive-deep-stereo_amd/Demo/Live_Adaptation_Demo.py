@@ -1,8 +1,9 @@
 """Live demo driver behind the reference's CLI (Demo/Live_Adaptation_Demo.py:15-71): a grabber thread feeds a one-slot queue, the
 RealTimeStereo thread adapts on every frame it takes from it.  Same flags; on top of them --frames (stop after N frames instead of
 waiting for a key press: headless runs), --output / --logDispStep (disparity PNGs, the windows' replacement), --device and
---rewardAsOnline.  --cameraName picks a registered source: 'Synthetic' and 'ImageList' ship with the package (grabber.py), camera SDK
-wrappers are registered by the user."""
+--rewardAsOnline, and --calibration (the source delivers RAW views, which are rectified on the device: madnet_hip/rectify.py).
+--cameraName picks a registered source: 'Synthetic' and 'ImageList' ship with the package (grabber.py), camera SDK wrappers are
+registered by the user."""
 import argparse
 import inspect
 import os
@@ -33,6 +34,7 @@ def build_parser():
     parser.add_argument("--SSIMTh", help="restore the initial network when the loss exceeds this value", type=float, default=0.5)
     parser.add_argument("--cameraConfig", help="json configuration of the frame source", default=None)
     parser.add_argument("--cameraName", help="registered frame source", default="Synthetic", choices=grabber.get_available_camera())
+    parser.add_argument("--calibration", help="json calibration of a raw camera pair (madnet_hip/rectify.py): the frames are rectified on the device before rescale and crop; default: the source delivers rectified frames", default=None)
     parser.add_argument("--frames", help="stop after this many frames (default: run until a key is pressed)", type=int, default=None)
     parser.add_argument("--framerate", help="target frames per second of the grabber (0 = as fast as the network takes them)", type=float, default=30)
     parser.add_argument("--output", help="folder for the disparity PNGs (16 bit, value*256)", default=None)
@@ -44,6 +46,7 @@ def build_parser():
 
 def main(args):
     assert args.cameraConfig is None or os.path.exists(args.cameraConfig)
+    assert args.calibration is None or os.path.exists(args.calibration)
     assert len(args.imageShape) in (1, 2) and len(args.cropShape) in (1, 2)
     on_frame = None
     if args.output is not None:
@@ -59,7 +62,7 @@ def main(args):
     dd = demo_model.RealTimeStereo(camera_frames, model_name=args.modelName, weight_path=args.weights, learning_rate=args.lr,
                                    block_config_path=args.blockConfig, image_shape=args.imageShape, crop_shape=args.cropShape,
                                    SSIMTh=args.SSIMTh, mode=args.mode, device=args.device, on_frame=on_frame, max_frames=args.frames,
-                                   reward_as_online=args.rewardAsOnline, allow_missing=not args.strictWeights)
+                                   reward_as_online=args.rewardAsOnline, allow_missing=not args.strictWeights, calibration=args.calibration)
     gg = grabber.get_camera(args.cameraName, camera_frames, config=args.cameraConfig, framerate=args.framerate)
     print('Threads ready to start')
     gg.start()

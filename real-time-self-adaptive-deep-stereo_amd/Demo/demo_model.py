@@ -60,9 +60,11 @@ class RealTimeStereo(threading.Thread):
     def __init__(self, camera_buffer, model_name='MADNet', weight_path=None, learning_rate=0.0001,
                  block_config_path='../block_config/MadNet_full.json', image_shape=[480, 640], crop_shape=[None, None],
                  SSIMTh=0.5, mode='MAD', device='cuda', on_frame=None, display=False, max_frames=None, reward_as_online=False,
-                 precision=None, _lib=None, allow_missing=True):
+                 precision=None, _lib=None, allow_missing=True, calibration=None):
         """allow_missing (default True, like the reference demo whose Saver restores the matching names and leaves the rest at their
-        initializer, weights_utils.get_var_to_restore_list): a checkpoint that lacks some model variables still loads."""
+        initializer, weights_utils.get_var_to_restore_list): a checkpoint that lacks some model variables still loads.
+        calibration (dict or JSON path, madnet_hip/rectify.py; default None: the camera delivers rectified frames): the frames are raw views and are
+        rectified on the device right after their upload, in front of rescale and crop."""
         if mode not in ('NONE', 'FULL', 'MAD'):
             raise ValueError('mode must be NONE, FULL or MAD')
         self._camera_buffer = camera_buffer
@@ -82,6 +84,10 @@ class RealTimeStereo(threading.Thread):
         self._precision = precision
         self._lib = _lib
         self._allow_missing = bool(allow_missing)
+        self._rectifier = None
+        if calibration is not None:
+            from madnet_hip.rectify import Rectifier
+            self._rectifier = Rectifier(_lib if _lib is not None else preprocessing._lib(), calibration, device)
         self._stop_flag = False
         self._adapter = None
         self.history = []                              # (loss, trained blocks, reset?) per processed frame
@@ -127,7 +133,10 @@ class RealTimeStereo(threading.Thread):
 
     def _prepare(self, frames):
         """[2,h,w,c] camera frames -> left, right [1,H,W,3] float32 device tensors of the network's shape."""
-        x = torch.as_tensor(np.ascontiguousarray(frames)[..., :3]).to(self._device, non_blocking=True).to(torch.float32)
+        if self._rectifier is not None:                # raw views: the 8-bit frames go up as they are, the remap kernel casts, picks the channels and rectifies
+            x = self._rectifier.apply(torch.as_tensor(np.ascontiguousarray(frames)).to(self._device, non_blocking=True))
+        else:
+            x = torch.as_tensor(np.ascontiguousarray(frames)[..., :3]).to(self._device, non_blocking=True).to(torch.float32)
         if self._image_shape is not None:
             x = preprocessing.rescale_image(x, self._image_shape)
         if self._crop_shape is not None:

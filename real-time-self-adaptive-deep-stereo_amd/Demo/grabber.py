@@ -1,6 +1,7 @@
 """Frame sources of the live demo behind the reference's grabber surface (Demo/grabber.py:13-29 factory, :36-92 ImageGrabber): a
 thread that reads rectified left/right frames and puts them, stacked as one [2,h,w,c] array, on the shared queue the adaptation
-thread (Demo/demo_model.RealTimeStereo) drains.
+thread (Demo/demo_model.RealTimeStereo) drains.  A source of RAW views (two plain cameras, a recording of them) needs no rectification
+of its own: RealTimeStereo(..., calibration=...) rectifies every pair on the device (madnet_hip/rectify.py).
 
 The camera SDK wrappers themselves (ZED Mini, Demo/grabber.py:100-150) need the vendor's Python module and the device; they are not
 part of this package.  A camera is added the way the reference's commented example does it: subclass ImageGrabber, give it a

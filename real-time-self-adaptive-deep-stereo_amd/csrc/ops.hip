@@ -1420,6 +1420,150 @@ extern "C" int mh_frame_prepare(const mh_frame_seg* segs, int32_t B, int32_t H, 
     return mh_check_launch("frame_apply");
 }
 
+// ---- the live demo's input side: rectification of raw camera views (mh_rectify_map, mh_remap; the reference leaves it to the grabber, README.MD:97) ----------------
+// mh_rectify_map: one lane per output pixel evaluates the formula of the header in its fp32 operations and their order, un-contracted, and stores one (x, y) pair
+// (8 bytes per lane, consecutive lanes consecutive pairs).  The V camera records travel as kernel arguments: the wave reads them with scalar loads.
+// mh_remap: a gather of a few MB that stays in L2 plus 12 bytes per pixel of writes.  A lane owns 4 consecutive output pixels = 2 float4 of the map and 3 float4 of
+// the interleaved output, like frame_apply_kernel (a lane per pixel would store 3 dwords at a 12-byte stride); its 16 taps are single-element loads.
+struct RectMapArgs { mh_camera_model cam[4]; float* map; int Wo, npix; };
+
+__device__ __forceinline__ void rectify_point(const mh_camera_model& c, int u, int v, float& mx, float& my) {
+    MH_FP_EXACT
+    const float x = ((float)u - c.cxn) / c.fxn, y = ((float)v - c.cyn) / c.fyn;
+    const float X = (c.R[0] * x + c.R[3] * y) + c.R[6];
+    const float Y = (c.R[1] * x + c.R[4] * y) + c.R[7];
+    const float W = (c.R[2] * x + c.R[5] * y) + c.R[8];
+    const float xp = X / W, yp = Y / W;
+    const float xx = xp * xp, yy = yp * yp, xy = xp * yp;
+    const float r2 = xx + yy;
+    const float r4 = r2 * r2;
+    const float r6 = r4 * r2;
+    const float rad = ((1.0f + c.k1 * r2) + c.k2 * r4) + c.k3 * r6;
+    const float xd = (xp * rad + (2.0f * c.p1) * xy) + c.p2 * (r2 + 2.0f * xx);
+    const float yd = (yp * rad + c.p1 * (r2 + 2.0f * yy)) + (2.0f * c.p2) * xy;
+    mx = c.fx * xd + c.cx;
+    my = c.fy * yd + c.cy;
+    const bool ok = W > 0.f && fabsf(mx) <= 3.402823466e+38f && fabsf(my) <= 3.402823466e+38f;      // (NaN fails every comparison)
+    if (!ok) { mx = -2.0f; my = -2.0f; }
+}
+
+// grid (ceil(npix / 256), V)
+__global__ __launch_bounds__(256) void rectify_map_kernel(RectMapArgs a) {
+    const int q = (int)blockIdx.x * 256 + (int)threadIdx.x;
+    if (q >= a.npix) return;
+    const int v = q / a.Wo, u = q - v * a.Wo;
+    float mx, my;
+    rectify_point(a.cam[blockIdx.y], u, v, mx, my);
+    float* dst = a.map + ((int64_t)blockIdx.y * a.npix + q) * 2;
+    if ((((uintptr_t)a.map) & 7u) == 0) {
+        float2 pair;
+        pair.x = mx; pair.y = my;
+        *reinterpret_cast<float2*>(dst) = pair;
+    } else { dst[0] = mx; dst[1] = my; }
+}
+
+struct RemapArgs { const void* src; const float* map; float* out; int Hs, Ws, Cs, u8, npix; };
+
+// the three output channels of source pixel (y, x) of the view whose first pixel is `view_px`; 0 outside the source (the address is then the view's first pixel)
+__device__ __forceinline__ void remap_tap(const RemapArgs& a, int64_t view_px, int y, int x, float (&s)[3]) {
+    const bool in = x >= 0 && x < a.Ws && y >= 0 && y < a.Hs;
+    const int64_t e = (view_px + (in ? (int64_t)y * a.Ws + x : 0)) * a.Cs;
+    const int c1 = a.Cs > 1 ? 1 : 0, c2 = a.Cs > 1 ? 2 : 0;            // Cs = 1: the one channel three times; Cs = 4: the fourth is never read
+    float r, g, b;
+    if (a.u8) {
+        const unsigned char* q = (const unsigned char*)a.src + e;
+        r = (float)q[0]; g = (float)q[c1]; b = (float)q[c2];
+    } else {
+        const float* q = (const float*)a.src + e;
+        r = q[0]; g = q[c1]; b = q[c2];
+    }
+    s[0] = in ? r : 0.f; s[1] = in ? g : 0.f; s[2] = in ? b : 0.f;
+}
+
+__device__ __forceinline__ void remap_pixel(const RemapArgs& a, int64_t view_px, float mx, float my, float* o) {
+    MH_FP_EXACT
+    o[0] = 0.f; o[1] = 0.f; o[2] = 0.f;
+    if (!(mx > -1.0f && mx < (float)a.Ws && my > -1.0f && my < (float)a.Hs)) return;        // no tap inside (NaN and the (-2, -2) mark come here)
+    const float x0f = floorf(mx), y0f = floorf(my);
+    const float tx = mx - x0f, ty = my - y0f;
+    const float ux = 1.0f - tx, uy = 1.0f - ty;
+    const int x0 = (int)x0f, y0 = (int)y0f;
+    float s00[3], s01[3], s10[3], s11[3];
+    remap_tap(a, view_px, y0, x0, s00); remap_tap(a, view_px, y0, x0 + 1, s01);
+    remap_tap(a, view_px, y0 + 1, x0, s10); remap_tap(a, view_px, y0 + 1, x0 + 1, s11);
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+        const float top = s00[c] * ux + s01[c] * tx;
+        const float bot = s10[c] * ux + s11[c] * tx;
+        o[c] = top * uy + bot * ty;
+    }
+}
+
+// grid (ceil(npix / 1024), V)
+__global__ __launch_bounds__(256) void remap_kernel(RemapArgs a) {
+    const int p0 = ((int)blockIdx.x * 256 + (int)threadIdx.x) * 4;
+    if (p0 >= a.npix) return;
+    const int view = blockIdx.y;
+    const bool full = p0 + 4 <= a.npix;
+    const float* m = a.map + ((int64_t)view * a.npix + p0) * 2;
+    float c[8];
+    if (full && (((uintptr_t)m) & 15u) == 0) {
+        const float4 m0 = reinterpret_cast<const float4*>(m)[0], m1 = reinterpret_cast<const float4*>(m)[1];
+        c[0] = m0.x; c[1] = m0.y; c[2] = m0.z; c[3] = m0.w; c[4] = m1.x; c[5] = m1.y; c[6] = m1.z; c[7] = m1.w;
+    } else {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const bool have = p0 + j < a.npix;
+            c[2 * j] = have ? m[have ? 2 * j : 0] : -2.0f; c[2 * j + 1] = have ? m[have ? 2 * j + 1 : 0] : -2.0f;
+        }
+    }
+    const int64_t view_px = (int64_t)view * a.Hs * a.Ws;
+    float v[12];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) remap_pixel(a, view_px, c[2 * j], c[2 * j + 1], v + 3 * j);
+    float* dst = a.out + ((int64_t)view * a.npix + p0) * 3;
+    if (full && (((uintptr_t)dst) & 15u) == 0) {
+#pragma unroll
+        for (int k = 0; k < 3; ++k) reinterpret_cast<float4*>(dst)[k] = make_float4(v[4 * k], v[4 * k + 1], v[4 * k + 2], v[4 * k + 3]);
+    } else {
+#pragma unroll
+        for (int k = 0; k < 12; ++k) if (p0 + k / 3 < a.npix) dst[k] = v[k];
+    }
+}
+
+static inline bool rectify_focal_ok(float f) { return f != 0.f && f == f && fabsf(f) <= 3.402823466e+38f; }
+
+extern "C" int mh_rectify_map(const mh_camera_model* cams, int32_t V, int32_t Ho, int32_t Wo, float* map, void* stream) {
+    MH_REQUIRE(cams && map, MH_ERR_ARG, "mh_rectify_map: null argument");
+    MH_REQUIRE(V >= 1 && V <= 4, MH_ERR_ARG, "mh_rectify_map: V = %d outside 1..4", V);
+    MH_REQUIRE(Ho > 0 && Wo > 0, MH_ERR_ARG, "mh_rectify_map: bad dimension");
+    for (int i = 0; i < V; ++i)
+        MH_REQUIRE(rectify_focal_ok(cams[i].fx) && rectify_focal_ok(cams[i].fy) && rectify_focal_ok(cams[i].fxn) && rectify_focal_ok(cams[i].fyn), MH_ERR_ARG,
+                   "mh_rectify_map: view %d has a zero or non-finite focal length", i);
+    MH_REQUIRE((int64_t)Ho * Wo * 3 < (1ll << 31), MH_ERR_UNSUPPORTED, "mh_rectify_map: output too large");
+    RectMapArgs a{};
+    for (int i = 0; i < V; ++i) a.cam[i] = cams[i];
+    a.map = map; a.Wo = Wo; a.npix = Ho * Wo;
+    hipLaunchKernelGGL(rectify_map_kernel, dim3((unsigned)((a.npix + 255) / 256), (unsigned)V), dim3(256), 0, (hipStream_t)stream, a);
+    mh_note_kernel("rectify_map_kernel grid %d x %d", (a.npix + 255) / 256, V);
+    return mh_check_launch("rectify_map");
+}
+
+extern "C" int mh_remap(const void* src, int32_t src_u8, const float* map, float* out, int32_t V, int32_t Hs, int32_t Ws, int32_t Cs, int32_t Ho, int32_t Wo,
+                        void* stream) {
+    MH_REQUIRE(src && map && out, MH_ERR_ARG, "mh_remap: null argument");
+    MH_REQUIRE(V >= 1 && V <= 4, MH_ERR_ARG, "mh_remap: V = %d outside 1..4", V);
+    MH_REQUIRE(Hs > 0 && Ws > 0 && Ho > 0 && Wo > 0, MH_ERR_ARG, "mh_remap: bad dimension");
+    MH_REQUIRE(Cs == 1 || Cs == 3 || Cs == 4, MH_ERR_ARG, "mh_remap: Cs = %d is not 1, 3 or 4", Cs);
+    MH_REQUIRE((int64_t)Hs * Ws <= (1ll << 31) / (V * Cs), MH_ERR_ARG, "mh_remap: more than 2^31 source elements");
+    MH_REQUIRE((int64_t)Ho * Wo * 3 < (1ll << 31), MH_ERR_UNSUPPORTED, "mh_remap: output too large");
+    RemapArgs a{};
+    a.src = src; a.map = map; a.out = out; a.Hs = Hs; a.Ws = Ws; a.Cs = Cs; a.u8 = src_u8 != 0; a.npix = Ho * Wo;
+    hipLaunchKernelGGL(remap_kernel, dim3((unsigned)((a.npix + 1023) / 1024), (unsigned)V), dim3(256), 0, (hipStream_t)stream, a);
+    mh_note_kernel("remap_kernel grid %d x %d", (a.npix + 1023) / 1024, V);
+    return mh_check_launch("remap");
+}
+
 // ---- proxy labels of the continual loop on the device (mh_sgm_proxy, mh_sgm_proxy_ex): census + four- or eight-path semi-global matching, 3x3 median --------------
 // Replaces the proxy column of the continual list (an external matcher's PNGs).  Integer arithmetic up to the sub-pixel step, no atomics, every launch writes
 // what the next one reads: the result does not depend on launch shape or order.  Workspace: census words [2][B][H][W] (8 bytes), one uint8 volume [B][H][W][D]

@@ -75,6 +75,11 @@ class FrameSeg(C.Structure):         # mh_frame_seg
                [(n, C.c_int32) for n in ("Hs", "Ws", "r0", "c0", "gt_kind", "active")] + [("delta", C.c_float), ("contrast", C.c_float), ("hue", C.c_float)]
 
 
+class CameraModel(C.Structure):      # mh_camera_model
+    _fields_ = [(n, C.c_float) for n in ("fx", "fy", "cx", "cy", "k1", "k2", "p1", "p2", "k3")] + [("R", C.c_float * 9)] + \
+               [(n, C.c_float) for n in ("fxn", "fyn", "cxn", "cyn")]
+
+
 class PlanRef(C.Structure):          # mh_plan_ref
     _fields_ = [("ops", C.c_void_p), ("nops", C.c_int32), ("reserved", C.c_int32)]
 
@@ -179,6 +184,8 @@ SIGNATURES = {
     "mh_host_device_pointer": (_I, [_P, C.POINTER(C.c_void_p)]),
     "mh_frame_prepare_ws_floats": (_L, [_I, _I, _I]),
     "mh_frame_prepare": (_I, [_P, _I, _I, _I, _P, _P, _P, _P, _P]),
+    "mh_rectify_map": (_I, [C.POINTER(CameraModel), _I, _I, _I, _P, _P]),
+    "mh_remap": (_I, [_P, _I, _P, _P, _I, _I, _I, _I, _I, _I, _P]),
     "mh_sgm_ws_bytes": (_L, [_I, _I, _I, _I]),
     "mh_sgm_proxy": (_I, [_P, _P, _I, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _P]),
     "mh_sgm_ws_bytes_ex": (_L, [_I, _I, _I, _I, _I, _I]),

@@ -564,6 +564,42 @@ def frame_prepare(lib, table, left, right, gt, ws=None, stream=None):
     lib.frame_prepare(C.c_void_p(ptr), B, H, W, _p(left), _p(right), _p(gt), _p(ws), _p(stream))
 
 
+def camera_model(K, D, R, P):
+    """mh_camera_model of one view: K 3x3 (raw camera matrix, no skew), D up to 5 distortion terms in OpenCV's order (missing ones are 0), R 3x3 rectifying
+    rotation, P 3x3 or 3x4 camera matrix of the rectified view (stereoRectify's; its fourth column is not read)"""
+    K, R, P = ([[float(v) for v in row] for row in m] for m in (K, R, P))
+    D = [float(v) for v in (D if D is not None else [])]
+    assert len(K) == 3 and len(R) == 3 and len(P) == 3 and len(D) <= 5 and all(len(row) == 3 for row in K + R) and all(len(row) in (3, 4) for row in P)
+    D = D + [0.0] * (5 - len(D))
+    c = _ffi.CameraModel()
+    c.fx, c.fy, c.cx, c.cy = K[0][0], K[1][1], K[0][2], K[1][2]
+    c.k1, c.k2, c.p1, c.p2, c.k3 = D
+    for k in range(9):
+        c.R[k] = R[k // 3][k % 3]
+    c.fxn, c.fyn, c.cxn, c.cyn = P[0][0], P[1][1], P[0][2], P[1][2]
+    return c
+
+
+def rectify_map(lib, cams, map_, stream=None):
+    """map_ [V,Ho,Wo,2] (float32, contiguous, written in every element) <- the raw-view position of every rectified pixel, per view from its camera_model
+    (mh_rectify_map: initUndistortRectifyMap's formula in fp32)"""
+    V, Ho, Wo, two = map_.shape
+    assert two == 2 and len(cams) == V and map_.dtype == torch.float32 and map_.is_contiguous()
+    arr = (_ffi.CameraModel * V)(*cams)
+    lib.rectify_map(arr, V, Ho, Wo, _p(map_), _p(stream))
+
+
+def remap(lib, src, map_, out, stream=None):
+    """out [V,Ho,Wo,3] (float32, contiguous, written in every element) <- src [V,Hs,Ws,Cs] (uint8 or float32, Cs = 1, 3 or 4) sampled bilinearly at
+    map_ [V,Ho,Wo,2] = (x, y), zero outside the source (mh_remap)"""
+    V, Hs, Ws, Cs = src.shape
+    _, Ho, Wo, _ = out.shape
+    assert tuple(map_.shape) == (V, Ho, Wo, 2) and tuple(out.shape) == (V, Ho, Wo, 3)
+    assert src.dtype in (torch.uint8, torch.float32) and src.is_contiguous()
+    assert all(t.dtype == torch.float32 and t.is_contiguous() for t in (map_, out))
+    lib.remap(_p(src), 1 if src.dtype == torch.uint8 else 0, _p(map_), _p(out), V, Hs, Ws, Cs, Ho, Wo, _p(stream))
+
+
 def shadow_cast(lib, pairs, device, keep, stream=None):
     """pairs: [(View src, Shadow dst)] -> every dst = bf16(src), ONE launch (mh_shadow_cast).  `keep` keeps the device table alive."""
     if not pairs:
