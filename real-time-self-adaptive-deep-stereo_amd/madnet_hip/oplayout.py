@@ -145,7 +145,10 @@ def pack(kind, values, sched=0):
     o.kind = kind
     oi, of, op = o.i, o.f, o.p          # (views of the record's own arrays)
     for k, name in L.i:
-        oi[k] = int(values[name])
+        v = int(values[name])
+        if not -0x80000000 <= v <= 0x7fffffff:      # (ctypes would store the low 32 bits without a word)
+            raise ValueError("%s: %s = %d does not fit the int32 slot i[%d]" % (L.name, name, v, k))
+        oi[k] = v
     for k, name in L.f:
         of[k] = float(values[name])
     for k, name in L.p:

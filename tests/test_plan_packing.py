@@ -149,5 +149,47 @@ def test_recorder_and_library_take_the_same_arguments():
     assert {n for n, f in inspect.getmembers(Recorder, inspect.isfunction) if not n.startswith("_")} - set(both) == NOT_OPS
 
 
+def test_pack_refuses_an_int_that_does_not_fit_its_slot():
+    """mh_fetch_inputs / mh_allreduce_sum take int64 counts, the record carries them in int32 slots: a count of 2^32 + 5 used to be recorded as 5 (ctypes
+    stores the low bits without a word) and the replay moved 5 elements where the direct call moved 2^32 + 5.  The error names kind and slot."""
+    import pytest
+    from madnet_hip import _ffi
+    from madnet_hip.plan import Recorder
+    for bad in (1 << 31, (1 << 32) + 5, -(1 << 31) - 1):
+        dst, counts = _tail(2, 1)
+        counts[1] = bad
+        with pytest.raises(ValueError, match=r"FETCH_INPUTS: count1 = %d .*i\[2\]" % bad):
+            Recorder().fetch_inputs(0x10000, dst, counts, 2, None)
+        bufs, counts = _tail(3, 0)
+        counts[0] = bad
+        with pytest.raises(ValueError, match=r"ALLREDUCE: count0 = %d .*i\[1\]" % bad):
+            Recorder().allreduce_sum(bufs, counts, 3, 0x10000, None)
+        with pytest.raises(ValueError, match=r"WARP_FWD: W = %d .*i\[4\]" % bad):
+            Recorder().warp_fwd(0x10000, 4, 0x20000, 0x30000, 4, 1, 2, bad, 4, None)
+        r = Recorder()
+        with pytest.raises(ValueError):
+            r.copy_channels(0x10000, bad, 0x20000, 4, 10, 2, 1.0, 0, None)
+        assert r.ops == []                      # nothing half-recorded
+
+
+def test_pack_keeps_the_int32_limits_and_the_bit_cast_grad_scale():
+    """the two ends of the range go in as they are; adam's grad_scale travels as a SIGNED 32-bit pattern (negative for a negative scale) and comes back
+    bit for bit"""
+    import struct
+    from madnet_hip import oplayout
+    from madnet_hip.plan import Recorder
+    for v in (-(1 << 31), (1 << 31) - 1, -1, 0):
+        dst, counts = _tail(1, 1)
+        counts[0] = v
+        r = Recorder()
+        r.fetch_inputs(0x10000, dst, counts, 1, None)
+        assert oplayout.fields(r.ops[0]).count0 == v
+    for gs in (-0.5, 1.0, -3.0e38, 1e-45, float("inf"), -0.0):
+        r = Recorder()
+        r.adam(0x10000, 0x20000, 0x30000, 0x40000, 77, 0x50000, 1e-3, 0.9, 0.999, 1e-8, gs, None)
+        bits_ = oplayout.fields(r.ops[0]).gs_bits
+        assert struct.pack("<i", bits_) == struct.pack("<f", gs), gs
+
+
 if __name__ == "__main__":
     open(GOLDEN, "w").write("[\n" + ",\n".join(json.dumps(rec, separators=(",", ":")) for rec in produce()) + "\n]\n")
