@@ -679,6 +679,34 @@ int mh_proxy_loss(const float* pred, const float* proxy, float* ws, float* resul
 int64_t mh_proxy_scaled_ws_floats(int32_t B, int32_t H, int32_t W, int32_t scale);
 int mh_proxy_loss_scaled(const float* pred, const float* proxy, float* ws, float* result, float* dpred, float weight,
                          float grad_scale, int32_t scale, int32_t B, int32_t H, int32_t W, void* stream);
+/* ---- the label losses of the reference's table: the six scalar losses that take (x, y, mask), the call get_supervised_loss / get_proxy_loss make
+ *      (Losses/loss_factory.py:28-108; additive: the ABI version stays).  With d = pred - label and v = valid:
+ *        loss                     phi(d)                                 phi'(d)            normaliser n
+ *        mean_l1 / sum_l1         |d|                                    sign(d), 0 at 0    sum(v) / 1
+ *        mean_l2 / sum_l2         d^2                                    2 d                sum(v) / 1
+ *        mean_huber / sum_huber   d > 1 ? 0.5 + (|d| - 1) : 0.5 d^2      d > 1 ? 1 : d      B * H * W / 1
+ *      The reference's quirks are kept: Huber tests the SIGNED d (tf.greater(diff, c), :57), so a large negative error stays quadratic, and d == 1 is
+ *      quadratic; mean_huber is tf.reduce_mean(huber * mask) (:71) and divides by the number of pixels, valid or not.
+ *   rule 0 (get_proxy_loss):      valid = !(label <= 0 || label >= hi)          (the reference's literal: hi = 192)
+ *   rule 1 (get_supervised_loss): valid = !(label == 0 || label >= hi)          (hi = max_disp)
+ *   result[0] = weight * sum(v * phi) / n;  result[1] = sum(v);  dpred (may be NULL) = grad_scale * weight * v * phi' / n, every element written.
+ *   No valid pixel: NaN for mean_l1 / mean_l2 (0 / 0, like the reference), 0 and a zero gradient for the other four.
+ * ws: mh_proxy_ws_floats() floats.  256 pixels per workgroup, float64 final reduction, no float atomics: two calls give the same bits, and
+ * MH_LOSS_MEAN_L1 gives the bits of mh_proxy_loss (rule 0, hi 192) / mh_supervised_loss (rule 1, hi max_disp), result and gradient.
+ * Launches: mean_l1, mean_l2: three (partial sums, final reduction, gradient; two without dpred).  sum_l1, sum_l2, mean_huber, sum_huber: two -- the
+ * normaliser does not depend on the data, so the first launch writes dpred as well.
+ * MH_ERR_ARG, nothing launched: loss outside 0 .. 5, rule outside 0 .. 1, hi <= 0, a null pred / label / ws / result, a non-positive dimension. */
+enum { MH_LOSS_MEAN_L1 = 0, MH_LOSS_SUM_L1, MH_LOSS_MEAN_L2, MH_LOSS_SUM_L2, MH_LOSS_MEAN_HUBER, MH_LOSS_SUM_HUBER };
+int mh_label_loss(const float* pred, const float* label, float* ws, float* result, float* dpred, int32_t loss, int32_t rule, float hi, float weight,
+                  float grad_scale, int32_t B, int32_t H, int32_t W, void* stream);
+/* the same six at 1/scale resolution, defined as mh_proxy_loss_scaled is, resize arithmetic included: p = R(pred), q = R(label) / scale, d = p - q,
+ * valid = !(q <= 0 || q >= 192) (the proxy rule, the literal 192); mean_huber divides by B * (H / scale) * (W / scale).  dpred [B,H,W] (may be NULL) =
+ * grad_scale * weight * R^T(v * phi') / n on the full grid, every element written.  ws: mh_proxy_scaled_ws_floats() floats.  MH_LOSS_MEAN_L1 gives the
+ * bits of mh_proxy_loss_scaled.  Launches: mean_l1, mean_l2: three (two without dpred); the other four: two (one launch takes the partial sums and
+ * walks the gradient).  MH_ERR_ARG, nothing launched: loss outside 0 .. 5, a null pred / label / ws / result, and the limits of mh_proxy_loss_scaled
+ * (0 < H, W < 65536, 1 <= scale <= min(H, W), B * H * W < 2^31). */
+int mh_label_loss_scaled(const float* pred, const float* label, float* ws, float* result, float* dpred, int32_t loss, float weight,
+                         float grad_scale, int32_t scale, int32_t B, int32_t H, int32_t W, void* stream);
 
 /* ---- offline training (Train.py): supervised mean_l1 per predicted scale and the Adam update -------------------------------
  * mh_supervised_loss: loss_factory.get_supervised_loss('mean_l1', multiScale=True, max_disp=MAX_DISP) term of ONE scale
@@ -761,11 +789,11 @@ uint32_t mh_crc32c(const void* data, int64_t n, uint32_t crc);
 enum { MH_OP_CONV = 1, MH_OP_WGRAD, MH_OP_CORR_FWD, MH_OP_CORR_BWD, MH_OP_WARP_FWD, MH_OP_WARP_BWD,
        MH_OP_RESIZE_FWD, MH_OP_RESIZE_BWD, MH_OP_PAD_REFLECT, MH_OP_LOSS, MH_OP_METRICS,
        MH_OP_MOMENTUM, MH_OP_COPY_CH, MH_OP_LEAKY_BWD, MH_OP_FILL, MH_OP_BIAS_GRAD,
-       MH_OP_WGRAD_PARTIAL, MH_OP_WGRAD_REDUCE, MH_OP_PROXY_LOSS, MH_OP_SUPERVISED_LOSS, MH_OP_ADAM, MH_OP_ADAM_ADVANCE,
+       MH_OP_WGRAD_PARTIAL, MH_OP_WGRAD_REDUCE, MH_OP_PROXY_LOSS /* i = B H W loss: loss 0 = mh_proxy_loss, else mh_label_loss with that MH_LOSS_*, rule 0, hi 192 */, MH_OP_SUPERVISED_LOSS, MH_OP_ADAM, MH_OP_ADAM_ADVANCE,
        MH_OP_RESIZE_IMAGE, MH_OP_LEVEL_FRONT, MH_OP_RESERVED_25 /* (was: transposed filter banks of the retired LDS-free kernel) */, MH_OP_PACK_W, MH_OP_CORR_WARP_BWD, MH_OP_SHADOW_CAST, MH_OP_WGRAD_STREAM, MH_OP_HEAD_BWD, MH_OP_HEAD_FWD, MH_OP_CONV_PLANES, MH_OP_PLANE_SPLIT, MH_OP_STAMP, MH_OP_CONV_PLANES_BWD, MH_OP_DET_FLUSH, MH_OP_CONV_IMAGE,
        MH_OP_ALLREDUCE /* mh_allreduce_sum: p[0] = comm, p[1 .. i[0]] = buffers, i[1 .. i[0]] = counts (floats, < 2^31 each) */,
        MH_OP_FETCH_INPUTS /* mh_fetch_inputs: p[0] = table, p[1 .. i[0]] = destinations, i[1 .. i[0]] = counts (floats, < 2^31 each) */,
-       MH_OP_PROXY_LOSS_SCALED /* mh_proxy_loss_scaled: i = B H W scale ; f = weight grad_scale ; p = pred proxy ws result dpred */,
+       MH_OP_PROXY_LOSS_SCALED /* mh_proxy_loss_scaled: i = B H W scale loss ; f = weight grad_scale ; p = pred proxy ws result dpred ; loss != 0: mh_label_loss_scaled with that MH_LOSS_* */,
        MH_OP_METRICS_KITTI /* mh_metrics_kitti: i = B H W ; p = disp gt ws result */ };
 /* i[26] of every op is its scheduling word: low byte = lane (0 = the caller's stream; 1..MH_MAX_LANES-1 = side
  * streams owned by the library: the op is forked from lane 0 right before it, i.e. ordered after everything recorded so

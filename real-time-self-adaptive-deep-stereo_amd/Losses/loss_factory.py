@@ -6,7 +6,9 @@
 
 Each returns compute_loss(disparities, inputs) like the reference; the per-scale terms are torch.autograd.Functions whose backward is the gradient the kernel
 wrote in the same launch.  Only the base losses the three scripts request by default are kernels ('mean_SSIM_l1' / 'mean_l1'); every other name of the
-reference's SUPERVISED_LOSS / PIXELWISE_LOSSES tables raises (out of scope)."""
+reference's SUPERVISED_LOSS / PIXELWISE_LOSSES tables raises (out of scope).  The other five scalar label losses of the reference (sum_l1, mean_l2, sum_l2,
+mean_huber, sum_huber) exist as a device op under both validity rules -- madnet_hip.ops.label_loss, Adapter(proxy_loss=), Stereo_Continual_Adaptation.py --proxyLoss --
+but not behind these builders."""
 import torch
 
 from madnet_hip import _ffi, ops

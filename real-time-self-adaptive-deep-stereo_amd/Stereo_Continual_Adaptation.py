@@ -1,7 +1,7 @@
 """Continual online adaptation with proxy labels on MI355X -- same flags, loop semantics and output files (overall.csv,
 series.csv, histogram.csv, params.sh, config.json, disparities/*.png, weights/model-<step>) as the reference script
 (Stereo_Continual_Adaptation.py:30-345).  Differences of the loop to Stereo_Online_Adaptation: the loss is the
-proxy-label mean_l1 (weight 0.01 full / 0.1 per MAD block, :75,112), the weights are only updated every --dilation
+proxy-label mean_l1 (weight 0.01 full / 0.1 per MAD block, :75,112; --proxyLoss puts another of the reference's label losses in its place), the weights are only updated every --dilation
 frames (:205), the reward update uses --decay / --uf (:218-221), the report is EPE + D1 (:241-249).
 The per-frame device work is madnet_hip.adapter.Adapter.step(left, right, gt, proxy).  --proxies sgm computes the proxy labels on the device
 (madnet_hip.proxy.ProxyMatcher over mh_sgm_proxy) instead of reading the list's fourth column."""
@@ -70,7 +70,8 @@ def main(args):
     adapter = Adapter(stereo_net, mode=args.mode, block_config=train_config, lr=args.lr, sample_mode=args.sampleMode,
                       num_blocks=args.numBlocks, fixed_id=args.fixedID, sample_frequency=args.sampleFrequency,
                       ssim_th=args.SSIMTh, reprojection_scale=args.reprojectionScale, loss='proxy',
-                      dilation=args.dilation, decay=args.decay, uf=args.uf, kitti_metrics=True)
+                      dilation=args.dilation, decay=args.decay, uf=args.uf, kitti_metrics=True,
+                      proxy_loss=getattr(args, 'proxyLoss', 'mean_l1'))
     avg_accumulator, d1_accumulator = [], []
     step = 0
     t_begin = time.time()
@@ -152,6 +153,7 @@ def build_parser():
     parser.add_argument("--uf", help="gain of the reward added to the logits of the last trained portions", type=float, default=0.01)
     parser.add_argument("--precision", help="MFMA arithmetic of the conv kernels: fp32 (default; the reference adapts in fp32), mixed (forward within fp32 tolerance, bf16 gradients) or bf16 (opt-in throughput mode)", choices=['fp32', 'mixed', 'bf16'], default='fp32')
     parser.add_argument("--proxies", help="where the proxy labels come from: list = the fourth column of the list (disparity PNGs of an external matcher); sgm = computed on the GPU from every frame pair (census + four-path semi-global matching; --proxyPaths 8 adds the diagonal paths, --proxyMedian a 3x3 median of the labels, --proxySpeckle N a speckle filter), the list then needs only left,right,gt", choices=['list', 'sgm'], default='list')
+    parser.add_argument("--proxyLoss", help="the loss on the proxy labels, one of the reference's six scalar label losses (Losses/loss_factory.py): mean_l1 is the reference script's; mean_huber / sum_huber are the robust ones (quadratic up to an error of 1 px, linear beyond -- on the positive side only, as in the reference); the sum_* forms and mean_huber do not divide by the number of valid labels, so their values are on another scale, and --SSIMTh is compared with whatever loss is chosen", choices=['mean_l1', 'sum_l1', 'mean_l2', 'sum_l2', 'mean_huber', 'sum_huber'], default='mean_l1')
     parser.add_argument("--proxyMaxDisp", help="--proxies sgm: number of disparities searched at full resolution (64, 128 or 192; with --proxyScale 2: 128, 256 or 384, the half-size frames are searched over half of it)", type=int, default=128)
     parser.add_argument("--proxyScale", help="--proxies sgm: 1 = match the frames as they are; 2 = match the half-size gray frames over --proxyMaxDisp / 2 disparities and write every label, doubled, to its 2 x 2 pixels (an eighth of the volume, about twice the mean label error, clearly worse on frames a few dozen rows high)", type=int, choices=[1, 2], default=1)
     parser.add_argument("--proxyPaths", help="--proxies sgm: aggregation paths, 4 = rows and columns, 8 = the four diagonals as well (fewer gross errors on full-size frames, worse on frames a few dozen rows high)", type=int, choices=[4, 8], default=4)

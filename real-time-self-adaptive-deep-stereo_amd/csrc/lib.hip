@@ -203,9 +203,13 @@ static int run_op(const mh_op& o, void* s) {
         }
         case MH_OP_ADAM_ADVANCE:
             return mh_adam_advance((float*)p[0], o.f[0], o.f[1], s);
-        case MH_OP_PROXY_LOSS:
+        case MH_OP_PROXY_LOSS:          // i[3] = loss: 0 (every record made before the slot existed) = mean_l1 through its own entry point
+            if (i[3] != 0)
+                return mh_label_loss((const float*)p[0], (const float*)p[1], (float*)p[2], (float*)p[3], (float*)p[4], i[3], 0, 192.0f, o.f[0], o.f[1], i[0], i[1], i[2], s);
             return mh_proxy_loss((const float*)p[0], (const float*)p[1], (float*)p[2], (float*)p[3], (float*)p[4], o.f[0], o.f[1], i[0], i[1], i[2], s);
-        case MH_OP_PROXY_LOSS_SCALED:
+        case MH_OP_PROXY_LOSS_SCALED:   // i[4] = loss, likewise
+            if (i[4] != 0)
+                return mh_label_loss_scaled((const float*)p[0], (const float*)p[1], (float*)p[2], (float*)p[3], (float*)p[4], i[4], o.f[0], o.f[1], i[3], i[0], i[1], i[2], s);
             return mh_proxy_loss_scaled((const float*)p[0], (const float*)p[1], (float*)p[2], (float*)p[3], (float*)p[4], o.f[0], o.f[1], i[3], i[0], i[1], i[2], s);
         case MH_OP_METRICS_KITTI:
             return mh_metrics_kitti((const float*)p[0], (const float*)p[1], (float*)p[2], (float*)p[3], i[0], i[1], i[2], s);

@@ -766,26 +766,51 @@ __global__ __launch_bounds__(256) void metrics_final_kernel(MetArgs p) {
 // ------------------------------------------------------------------------------------------
 // The supervised multi-scale loss of Train.py (loss_factory.get_supervised_loss('mean_l1'), Losses/loss_factory.py:256-302) is the
 // same reduction with valid = !(target == 0 || target >= max_disp): `hi` / `zero_only` select the rule.
-struct ProxyArgs { const float* pred; const float* proxy; float* part; float* result; float* dpred; int64_t total; int nblk; float weight, gs; float hi; int zero_only; };
+//
+// mh_label_loss: the same reduction for the six scalar (x, y, mask) losses of the reference's table (Losses/loss_factory.py:28-108), FAM = the per-pixel term
+//   0  l1     phi = |d|                                  phi' = sign(d), 0 at 0
+//   1  l2     phi = d^2                                  phi' = 2 d
+//   2  huber  phi = d > 1 ? 0.5 + (|d| - 1) : 0.5 d^2    phi' = d > 1 ? 1 : d       (:52-58: the test is on the SIGNED d -- a large negative error stays
+//                                                                                    quadratic -- and d == 1 is quadratic)
+// and `norm` = the normaliser where it does not depend on the data (sum_*: 1; mean_huber: the number of pixels, valid or not -- tf.reduce_mean(huber * mask), :71),
+// 0 = sum(valid) (mean_l1, mean_l2).  With a fixed normaliser the partial kernel writes the gradient too (FUSED) and the op is two launches.  The kernels are
+// templated on FAM: FAM 0 with norm 0 is the code mh_proxy_loss / mh_supervised_loss always ran, so MH_LOSS_MEAN_L1 has their bits.
+struct ProxyArgs { const float* pred; const float* proxy; float* part; float* result; float* dpred; int64_t total; int nblk; float weight, gs; float hi; int zero_only;
+                   float norm; };
 __device__ __forceinline__ float proxy_valid(const ProxyArgs& p, float px) {
     const bool bad = (p.zero_only ? px == 0.f : px <= 0.f) || px >= p.hi;
     return bad ? 0.f : 1.f;
 }
 
-__global__ __launch_bounds__(256) void proxy_partial_kernel(ProxyArgs p) {
+template <int FAM> __device__ __forceinline__ float label_phi(float d) {
+    if (FAM == 0) return fabsf(d);
+    if (FAM == 1) return d * d;
+    return d > 1.0f ? 0.5f + (fabsf(d) - 1.0f) : 0.5f * (d * d);
+}
+
+template <int FAM> __device__ __forceinline__ float label_dphi(float d) {
+    if (FAM == 0) return d > 0.f ? 1.f : (d < 0.f ? -1.f : 0.f);
+    if (FAM == 1) return 2.0f * d;
+    return d > 1.0f ? 1.0f : d;
+}
+
+template <int FAM, bool FUSED> __global__ __launch_bounds__(256) void proxy_partial_kernel(ProxyArgs p) {
     __shared__ float red[4];
     const int64_t q = (int64_t)blockIdx.x * 256 + threadIdx.x;
     float e = 0.f, v = 0.f;
     if (q < p.total) {
         const float px = p.proxy[q];
         v = proxy_valid(p, px);
-        e = fabsf(p.pred[q] - px) * v;
+        const float d = p.pred[q] - px;
+        e = label_phi<FAM>(d) * v;
+        if (FUSED) p.dpred[q] = p.gs * p.weight * v * label_dphi<FAM>(d) / p.norm;
     }
     const float se = block_sum(e, red);
     const float sv = block_sum(v, red);
     if (threadIdx.x == 0) { p.part[blockIdx.x * 2 + 0] = se; p.part[blockIdx.x * 2 + 1] = sv; }
 }
 
+// (norm > 0: the fixed normaliser instead of sum(valid))
 __global__ __launch_bounds__(256) void proxy_final_kernel(ProxyArgs p) {
     __shared__ double red[2][256];
     double a = 0, c = 0;
@@ -797,19 +822,19 @@ __global__ __launch_bounds__(256) void proxy_final_kernel(ProxyArgs p) {
         __syncthreads();
     }
     if (threadIdx.x == 0) {
-        p.result[0] = (float)((double)p.weight * red[0][0] / red[1][0]);      // 0/0 = NaN like the TF graph
+        const double n = p.norm > 0.f ? (double)p.norm : red[1][0];
+        p.result[0] = (float)((double)p.weight * red[0][0] / n);              // 0/0 = NaN like the TF graph
         p.result[1] = (float)red[1][0];
     }
 }
 
-__global__ __launch_bounds__(256) void proxy_grad_kernel(ProxyArgs p) {
+template <int FAM> __global__ __launch_bounds__(256) void proxy_grad_kernel(ProxyArgs p) {
     const int64_t q = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (q >= p.total) return;
     const float px = p.proxy[q];
     const float v = proxy_valid(p, px);
     const float d = p.pred[q] - px;
-    const float sgn = d > 0.f ? 1.f : (d < 0.f ? -1.f : 0.f);
-    p.dpred[q] = p.gs * p.weight * v * sgn / p.result[1];
+    p.dpred[q] = p.gs * p.weight * v * label_dphi<FAM>(d) / p.result[1];
 }
 
 // ------------------------------------------------------------------------------------------
@@ -820,7 +845,10 @@ __global__ __launch_bounds__(256) void proxy_grad_kernel(ProxyArgs p) {
 // Both maps are sampled on the fly -- launch 1 for the partial sums, launch 3 again per candidate output pixel of a source pixel (the gather
 // walk of resize_bwd_kernel, fixed order, no atomics, every element of dpred written); launch 2 is proxy_final_kernel.
 // ------------------------------------------------------------------------------------------
-struct ProxySArgs { const float* pred; const float* proxy; float* part; const float* result; float* dpred; int B, H, W, Hs, Ws; float sy, sx, fs, weight, gs; };
+// mh_label_loss_scaled: FAM / norm as for ProxyArgs above (mean_huber: norm = B * Hs * Ws).  With a fixed normaliser ONE launch does both walks
+// (proxy_s_fused_kernel: the partial sums by its first workgroups, the gather walk by all of them), so the op is two launches.
+struct ProxySArgs { const float* pred; const float* proxy; float* part; const float* result; float* dpred; int B, H, W, Hs, Ws; float sy, sx, fs, weight, gs;
+                    float norm; };
 
 // interp1 without mul+sub contraction: t is EXACTLY fl(i * scale) - lo.  Where fl(i * scale) is an integer (row 21 of 128 -> 42 rows: 21 * fl(128 / 42) rounds to 64) the
 // upper tap must carry the weight 0, not the 5e-7 an fma leaves behind: a label whose lower taps are holes (exactly 0) is then exactly 0 -- invalid -- in both launches
@@ -844,8 +872,7 @@ __device__ __forceinline__ float proxy_s_diff(const ProxySArgs& p, const float* 
     return pv - q;
 }
 
-__global__ __launch_bounds__(256) void proxy_s_partial_kernel(ProxySArgs p) {
-    __shared__ float red[4];
+template <int FAM> __device__ __forceinline__ void proxy_s_partial(const ProxySArgs& p, float* red) {
     const int64_t total = (int64_t)p.B * p.Hs * p.Ws;
     const int64_t q = (int64_t)blockIdx.x * 256 + threadIdx.x;
     float e = 0.f, v = 0.f;
@@ -857,7 +884,7 @@ __global__ __launch_bounds__(256) void proxy_s_partial_kernel(ProxySArgs p) {
         int y0, y1, x0, x1; float ty, tx;
         interp1_exact(y, p.sy, p.H, y0, y1, ty);
         interp1_exact(x, p.sx, p.W, x0, x1, tx);
-        e = fabsf(proxy_s_diff(p, p.pred + off, p.proxy + off, y0, y1, ty, x0, x1, tx, v)) * v;
+        e = label_phi<FAM>(proxy_s_diff(p, p.pred + off, p.proxy + off, y0, y1, ty, x0, x1, tx, v)) * v;
     }
     const float se = block_sum(e, red);
     const float sv = block_sum(v, red);
@@ -865,11 +892,10 @@ __global__ __launch_bounds__(256) void proxy_s_partial_kernel(ProxySArgs p) {
 }
 
 // one lane per SOURCE pixel: the output pixels whose lower / upper tap is this pixel, rows outside, columns inside (resize_bwd_kernel's candidate window)
-__global__ __launch_bounds__(256) void proxy_s_grad_kernel(ProxySArgs p) {
+template <int FAM> __device__ __forceinline__ void proxy_s_grad(const ProxySArgs& p, float nvalid) {
     const int64_t total = (int64_t)p.B * p.H * p.W;
     const float isy = 1.0f / p.sy, isx = 1.0f / p.sx;
     const float k = p.gs * p.weight;
-    const float nvalid = p.result[1];
     for (int64_t q = (int64_t)blockIdx.x * 256 + threadIdx.x; q < total; q += (int64_t)gridDim.x * 256) {
         const int sx = (int)(q % p.W);
         const int64_t t2 = q / p.W;
@@ -890,12 +916,26 @@ __global__ __launch_bounds__(256) void proxy_s_grad_kernel(ProxySArgs p) {
                 if (wx == 0.f) continue;
                 float v;
                 const float d = proxy_s_diff(p, p.pred + off, p.proxy + off, y0, y1, ty, x0, x1, tx, v);
-                const float sgn = d > 0.f ? 1.f : (d < 0.f ? -1.f : 0.f);
+                const float sgn = label_dphi<FAM>(d);
                 acc += v * sgn * wy * wx;
             }
         }
         p.dpred[q] = k * acc / nvalid;
     }
+}
+
+template <int FAM> __global__ __launch_bounds__(256) void proxy_s_partial_kernel(ProxySArgs p) {
+    __shared__ float red[4];
+    proxy_s_partial<FAM>(p, red);
+}
+
+template <int FAM> __global__ __launch_bounds__(256) void proxy_s_grad_kernel(ProxySArgs p) { proxy_s_grad<FAM>(p, p.result[1]); }
+
+// fixed normaliser: workgroups 0 .. nblk - 1 first take their 256 output pixels' partial sums, then every workgroup joins the gather walk
+template <int FAM> __global__ __launch_bounds__(256) void proxy_s_fused_kernel(ProxySArgs p, int nblk) {
+    __shared__ float red[4];
+    if ((int)blockIdx.x < nblk) proxy_s_partial<FAM>(p, red);
+    proxy_s_grad<FAM>(p, p.norm);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -2587,12 +2627,46 @@ static int masked_l1(const char* what, const float* pred, const float* target, f
                      float grad_scale, float hi, int zero_only, int32_t B, int32_t H, int32_t W, void* stream) {
     MH_REQUIRE(pred && target && ws && result, MH_ERR_ARG, "%s: null argument", what);
     MH_REQUIRE(B > 0 && H > 0 && W > 0, MH_ERR_ARG, "%s: bad dimension", what);
-    ProxyArgs a{pred, target, ws, result, dpred, (int64_t)B * H * W, (int)nblk((int64_t)B * H * W), weight, grad_scale, hi, zero_only};
+    ProxyArgs a{pred, target, ws, result, dpred, (int64_t)B * H * W, (int)nblk((int64_t)B * H * W), weight, grad_scale, hi, zero_only, 0.f};
     hipStream_t s = (hipStream_t)stream;
-    hipLaunchKernelGGL(proxy_partial_kernel, dim3(a.nblk), dim3(256), 0, s, a);
+    hipLaunchKernelGGL((proxy_partial_kernel<0, false>), dim3(a.nblk), dim3(256), 0, s, a);
     hipLaunchKernelGGL(proxy_final_kernel, dim3(1), dim3(256), 0, s, a);
-    if (dpred) hipLaunchKernelGGL(proxy_grad_kernel, dim3(a.nblk), dim3(256), 0, s, a);
+    if (dpred) hipLaunchKernelGGL((proxy_grad_kernel<0>), dim3(a.nblk), dim3(256), 0, s, a);
     return mh_check_launch(what);
+}
+
+// the launches of mh_label_loss for one per-pixel term: a.norm > 0 = fixed normaliser, the gradient leaves with the partial sums
+template <int FAM> static void label_loss_launch(const ProxyArgs& a, hipStream_t s) {
+    const bool fused = a.norm > 0.f && a.dpred;
+    if (fused) hipLaunchKernelGGL((proxy_partial_kernel<FAM, true>), dim3(a.nblk), dim3(256), 0, s, a);
+    else hipLaunchKernelGGL((proxy_partial_kernel<FAM, false>), dim3(a.nblk), dim3(256), 0, s, a);
+    hipLaunchKernelGGL(proxy_final_kernel, dim3(1), dim3(256), 0, s, a);
+    if (a.dpred && !fused) hipLaunchKernelGGL((proxy_grad_kernel<FAM>), dim3(a.nblk), dim3(256), 0, s, a);
+}
+
+// normaliser of loss `loss` over npix pixels: 0 = sum(valid) (mean_l1, mean_l2), 1 (sum_*), npix (mean_huber)
+static inline float label_loss_norm(int32_t loss, int64_t npix) {
+    if (loss == MH_LOSS_MEAN_L1 || loss == MH_LOSS_MEAN_L2) return 0.f;
+    return loss == MH_LOSS_MEAN_HUBER ? (float)npix : 1.0f;
+}
+
+extern "C" int mh_label_loss(const float* pred, const float* label, float* ws, float* result, float* dpred, int32_t loss, int32_t rule, float hi, float weight,
+                             float grad_scale, int32_t B, int32_t H, int32_t W, void* stream) {
+    MH_REQUIRE(pred && label && ws && result, MH_ERR_ARG, "mh_label_loss: null argument");
+    MH_REQUIRE(loss >= MH_LOSS_MEAN_L1 && loss <= MH_LOSS_SUM_HUBER, MH_ERR_ARG, "mh_label_loss: loss must be one of MH_LOSS_* (0 .. 5)");
+    MH_REQUIRE(rule == 0 || rule == 1, MH_ERR_ARG, "mh_label_loss: rule must be 0 (proxy) or 1 (supervised)");
+    MH_REQUIRE(hi > 0.f, MH_ERR_ARG, "mh_label_loss: hi must be positive");
+    MH_REQUIRE(B > 0 && H > 0 && W > 0, MH_ERR_ARG, "mh_label_loss: bad dimension");
+    const int64_t npix = (int64_t)B * H * W;
+    MH_REQUIRE(nblk(npix) < (1ll << 31), MH_ERR_ARG, "mh_label_loss: too many pixels");
+    ProxyArgs a{pred, label, ws, result, dpred, npix, (int)nblk(npix), weight, grad_scale, hi, rule, label_loss_norm(loss, npix)};
+    hipStream_t s = (hipStream_t)stream;
+    switch (loss >> 1) {
+        case 0: label_loss_launch<0>(a, s); break;
+        case 1: label_loss_launch<1>(a, s); break;
+        default: label_loss_launch<2>(a, s); break;
+    }
+    return mh_check_launch("mh_label_loss");
 }
 
 extern "C" int mh_proxy_loss(const float* pred, const float* proxy, float* ws, float* result, float* dpred, float weight,
@@ -2611,22 +2685,45 @@ extern "C" int64_t mh_proxy_scaled_ws_floats(int32_t B, int32_t H, int32_t W, in
     return 2 * nblk((int64_t)B * (H / scale) * (W / scale));
 }
 
-extern "C" int mh_proxy_loss_scaled(const float* pred, const float* proxy, float* ws, float* result, float* dpred, float weight,
-                                    float grad_scale, int32_t scale, int32_t B, int32_t H, int32_t W, void* stream) {
-    MH_REQUIRE(pred && proxy && ws && result, MH_ERR_ARG, "mh_proxy_loss_scaled: null argument");
-    MH_REQUIRE(B > 0 && H > 0 && W > 0 && H < 65536 && W < 65536, MH_ERR_ARG, "mh_proxy_loss_scaled: bad dimension");
-    MH_REQUIRE(scale >= 1 && scale <= H && scale <= W, MH_ERR_ARG, "mh_proxy_loss_scaled: scale must lie in 1 .. min(H, W)");
+template <int FAM> static void label_loss_scaled_launch(const ProxySArgs& a, const ProxyArgs& f, hipStream_t s) {
+    const int ggrid = grid_for((int64_t)a.B * a.H * a.W);
+    const bool fused = a.norm > 0.f && a.dpred;
+    if (fused) hipLaunchKernelGGL((proxy_s_fused_kernel<FAM>), dim3(f.nblk > ggrid ? f.nblk : ggrid), dim3(256), 0, s, a, f.nblk);
+    else hipLaunchKernelGGL((proxy_s_partial_kernel<FAM>), dim3(f.nblk), dim3(256), 0, s, a);
+    hipLaunchKernelGGL(proxy_final_kernel, dim3(1), dim3(256), 0, s, f);
+    if (a.dpred && !fused) hipLaunchKernelGGL((proxy_s_grad_kernel<FAM>), dim3(ggrid), dim3(256), 0, s, a);
+}
+
+static int label_loss_scaled(const char* what, const float* pred, const float* proxy, float* ws, float* result, float* dpred, int32_t loss, float weight,
+                             float grad_scale, int32_t scale, int32_t B, int32_t H, int32_t W, void* stream) {
+    MH_REQUIRE(pred && proxy && ws && result, MH_ERR_ARG, "%s: null argument", what);
+    MH_REQUIRE(loss >= MH_LOSS_MEAN_L1 && loss <= MH_LOSS_SUM_HUBER, MH_ERR_ARG, "%s: loss must be one of MH_LOSS_* (0 .. 5)", what);
+    MH_REQUIRE(B > 0 && H > 0 && W > 0 && H < 65536 && W < 65536, MH_ERR_ARG, "%s: bad dimension", what);
+    MH_REQUIRE(scale >= 1 && scale <= H && scale <= W, MH_ERR_ARG, "%s: scale must lie in 1 .. min(H, W)", what);
     const int Hs = H / scale, Ws = W / scale;
     const int64_t nout = (int64_t)B * Hs * Ws;
-    MH_REQUIRE((int64_t)B * H * W < (1ll << 31), MH_ERR_ARG, "mh_proxy_loss_scaled: too many pixels");
-    ProxySArgs a{pred, proxy, ws, result, dpred, B, H, W, Hs, Ws, (float)H / (float)Hs, (float)W / (float)Ws, (float)scale, weight, grad_scale};
+    MH_REQUIRE((int64_t)B * H * W < (1ll << 31), MH_ERR_ARG, "%s: too many pixels", what);
+    const float norm = label_loss_norm(loss, nout);
+    ProxySArgs a{pred, proxy, ws, result, dpred, B, H, W, Hs, Ws, (float)H / (float)Hs, (float)W / (float)Ws, (float)scale, weight, grad_scale, norm};
     ProxyArgs f{};                                                     // (the final reduction is the un-scaled loss's)
-    f.part = ws; f.result = result; f.nblk = (int)nblk(nout); f.weight = weight;
+    f.part = ws; f.result = result; f.nblk = (int)nblk(nout); f.weight = weight; f.norm = norm;
     hipStream_t s = (hipStream_t)stream;
-    hipLaunchKernelGGL(proxy_s_partial_kernel, dim3(f.nblk), dim3(256), 0, s, a);
-    hipLaunchKernelGGL(proxy_final_kernel, dim3(1), dim3(256), 0, s, f);
-    if (dpred) hipLaunchKernelGGL(proxy_s_grad_kernel, dim3(grid_for((int64_t)B * H * W)), dim3(256), 0, s, a);
-    return mh_check_launch("mh_proxy_loss_scaled");
+    switch (loss >> 1) {
+        case 0: label_loss_scaled_launch<0>(a, f, s); break;
+        case 1: label_loss_scaled_launch<1>(a, f, s); break;
+        default: label_loss_scaled_launch<2>(a, f, s); break;
+    }
+    return mh_check_launch(what);
+}
+
+extern "C" int mh_proxy_loss_scaled(const float* pred, const float* proxy, float* ws, float* result, float* dpred, float weight,
+                                    float grad_scale, int32_t scale, int32_t B, int32_t H, int32_t W, void* stream) {
+    return label_loss_scaled("mh_proxy_loss_scaled", pred, proxy, ws, result, dpred, MH_LOSS_MEAN_L1, weight, grad_scale, scale, B, H, W, stream);
+}
+
+extern "C" int mh_label_loss_scaled(const float* pred, const float* label, float* ws, float* result, float* dpred, int32_t loss, float weight,
+                                    float grad_scale, int32_t scale, int32_t B, int32_t H, int32_t W, void* stream) {
+    return label_loss_scaled("mh_label_loss_scaled", pred, label, ws, result, dpred, loss, weight, grad_scale, scale, B, H, W, stream);
 }
 
 extern "C" int64_t mh_metrics_kitti_ws_floats(int32_t B, int32_t H, int32_t W) { return 3 * nblk((int64_t)B * H * W) + 16; }

@@ -38,6 +38,8 @@ class Op(C.Structure):
 COMM_ID_BYTES = 128            # MH_COMM_ID_BYTES
 ALLREDUCE_MAX_BUFS = 8         # MH_ALLREDUCE_MAX_BUFS
 FETCH_MAX = 4                  # MH_FETCH_MAX
+# MH_LOSS_*: name -> the `loss` argument of mh_label_loss / mh_label_loss_scaled and the `loss` slot of a PROXY_LOSS / PROXY_LOSS_SCALED record
+LABEL_LOSS = {"mean_l1": 0, "sum_l1": 1, "mean_l2": 2, "sum_l2": 3, "mean_huber": 4, "sum_huber": 5}
 
 
 class InputTable(C.Structure):     # mh_input_table
@@ -162,6 +164,8 @@ SIGNATURES = {
     "mh_proxy_scaled_ws_floats": (_L, [_I, _I, _I, _I]),
     "mh_proxy_loss_scaled": (_I, [_P, _P, _P, _P, _P, _F, _F, _I, _I, _I, _I, _P]),
     "mh_supervised_loss": (_I, [_P, _P, _P, _P, _P, _F, _F, _F, _I, _I, _I, _P]),
+    "mh_label_loss": (_I, [_P, _P, _P, _P, _P, _I, _I, _F, _F, _F, _I, _I, _I, _P]),
+    "mh_label_loss_scaled": (_I, [_P, _P, _P, _P, _P, _I, _F, _F, _I, _I, _I, _I, _P]),
     "mh_adam": (_I, [_P, _P, _P, _P, _L, _P, _F, _F, _F, _F, _F, _P]),
     "mh_adam_advance": (_I, [_P, _F, _F, _P]),
     "mh_corr_fwd": (_I, [_P, _I, _P, _I, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P]),

@@ -20,6 +20,7 @@ import numpy as np
 import torch
 
 from Sampler import sampler_factory
+from . import _ffi
 from . import engine as E
 from . import ops
 
@@ -34,10 +35,13 @@ class Adapter(object):
                  num_blocks=1, fixed_id=0, sample_frequency=1, ssim_th=0.5, reprojection_scale=1,
                  use_graph=True, shared_model=False, process_group=None, loss="reprojection", dilation=1, decay=0.99, uf=0.01,
                  optimizer="momentum", reset_optimizer=False, reward_every_step_first=False, early_reduce=None, in_graph_collective=None, fetch_inputs=None,
-                 kitti_metrics=False):
+                 kitti_metrics=False, proxy_loss="mean_l1"):
         """loss='proxy', dilation, decay, uf: the continual-adaptation variant (Stereo_Continual_Adaptation.py:75-112,
         205-249, 302-304): proxy-label mean_l1 loss, weight update only every `dilation`-th frame, reward update
         sample_distribution = decay * sample_distribution (+ uf * gain on the last trained blocks).
+        proxy_loss (loss='proxy' only): which of the reference's six scalar label losses goes on the proxy labels -- mean_l1 (the reference script's), sum_l1,
+        mean_l2, sum_l2, mean_huber, sum_huber (_ffi.LABEL_LOSS; Losses/loss_factory.py:28-108) -- in the full-resolution loss and the MAD blocks' losses alike,
+        with the weights of mean_l1 (0.01 / 0.1); the reset test against ssim_th and the MAD reward read its value where they read mean_l1's.
         optimizer='adam', reset_optimizer, reward_every_step_first: the live demo's variant of the loop (Demo/demo_model.py:164,
         203-208, 253-262): tf.train.AdamOptimizer(lr) instead of momentum; a reset without a weight file re-runs the initialisers,
         i.e. also clears the optimizer slots; its `first` flag is never cleared, so every step re-seeds both remembered losses.
@@ -50,12 +54,18 @@ class Adapter(object):
             raise ValueError("mode must be NONE, FULL or MAD")
         if loss not in ("reprojection", "proxy"):
             raise ValueError("loss must be 'reprojection' or 'proxy'")
+        if proxy_loss not in _ffi.LABEL_LOSS:
+            raise ValueError("proxy_loss must be one of %s" % ", ".join(_ffi.LABEL_LOSS))
+        if proxy_loss != "mean_l1" and loss != "proxy":
+            raise ValueError("proxy_loss needs loss='proxy'")
         self.net, self.eng, self.lib = net, net.engine, net._lib
         self.loss, self.dilation, self.decay, self.uf = loss, max(1, int(dilation)), decay, uf
+        self.proxy_loss = proxy_loss
         if loss == "proxy":
             if not hasattr(self.eng, "proxy"):
                 raise NotImplementedError("the proxy-label loss needs an engine with a proxy buffer")
             self.eng.loss_kind = "proxy"
+            self.eng.proxy_loss = proxy_loss
         self.kitti = bool(kitti_metrics)
         if self.kitti:
             self.eng.kitti_metrics = True
@@ -300,7 +310,7 @@ class Adapter(object):
 
 class MultiAdapter(object):
     """S stereo streams with PRIVATE models on ONE GPU ("several streams per GPU may be batched"): every stream keeps its own
-    Adapter -- weights, optimizer state, sampler, reward logic, reset -- and one step() advances all of them; the S step plans run as parallel
+    Adapter -- weights, optimizer state, sampler, reward logic, reset, its loss and proxy_loss -- and one step() advances all of them; the S step plans run as parallel
     branches of ONE hipGraph (mh_plans_run), one graph per combination of plan keys (FULL / NONE: one; MAD: the sampled blocks of every stream).
     The models' chains are serial inside their branch (engine.wgrad_lanes = 0, set here before any plan is built)."""
 

@@ -103,6 +103,7 @@ class DispNetEngine(EngineBase):
         # continual-adaptation variant (loss_kind = 'proxy'): proxy labels + the mean_l1 loss workspace
         self.proxy = z(B, H, W); self.proxy_ws = z(lib.proxy_ws_floats(B, H, W))
         self.loss_kind = "reprojection"
+        self.proxy_loss = "mean_l1"       # loss_kind 'proxy': which of _ffi.LABEL_LOSS goes on the labels (Adapter(proxy_loss=))
         self.loss_ws = z(lib.loss_ws_floats(B, H, W)); self.met_ws = z(lib.metrics_ws_floats(B, H, W))
         self.res_loss = self.params.g_loss[self.params.total:self.params.total + 4]; self.res_met = z(4)   # (loss result behind the gradients: one collective carries both)
         self.ops = []
@@ -355,12 +356,12 @@ class DispNetEngine(EngineBase):
                        mul=float(self.Wp) / float(n.st.W), mode=1)
 
     def record_loss_metrics(self, r, with_grad):
-        """full-resolution reprojection loss -- or, loss_kind 'proxy', full_proxy_loss of the continual variant (Stereo_Continual_Adaptation.py:75: mean_l1 against the
+        """full-resolution reprojection loss -- or, loss_kind 'proxy', full_proxy_loss of the continual variant (Stereo_Continual_Adaptation.py:75: self.proxy_loss, default mean_l1, against the
         proxy labels, weight 0.01; of the reduced multi-scale sum only the last prediction contributes) -- + EPE / bad3"""
         if self.loss_kind not in ("reprojection", "proxy"):
             raise ValueError("loss_kind must be 'reprojection' or 'proxy'")
         if self.loss_kind == "proxy":
-            ops.proxy_loss(r, self.pred, self.proxy, self.proxy_ws, self.res_loss, self.dpred if with_grad else None, weight=0.01)
+            ops.proxy_loss(r, self.pred, self.proxy, self.proxy_ws, self.res_loss, self.dpred if with_grad else None, weight=0.01, loss=self.proxy_loss)
         else:
             ops.reprojection_loss(r, self.left, self.right, self.pred, self.loss_ws, self.res_loss, self.dpred if with_grad else None)
         self.record_metrics(r)

@@ -145,6 +145,7 @@ class MadNetEngine(EngineBase, ElisionPasses, BackwardRecorder):
         self.proxy = z(B, self.H0, self.W0)
         self.proxy_ws = z(self.lib.proxy_ws_floats(B, self.H0, self.W0))
         self.loss_kind = "reprojection"
+        self.proxy_loss = "mean_l1"       # loss_kind 'proxy': which of _ffi.LABEL_LOSS goes on the labels (Adapter(proxy_loss=)); the workspaces serve all six
         self.rscale = 1
 
     def set_reprojection_scale(self, s):
@@ -488,12 +489,12 @@ class MadNetEngine(EngineBase, ElisionPasses, BackwardRecorder):
 
     def record_loss_metrics(self, r, with_grad):
         """full-resolution reprojection loss (Stereo_Online_Adaptation.py:70) -- or, loss_kind 'proxy', the proxy-label
-        mean_l1 of the continual variant (Stereo_Continual_Adaptation.py:75, weight 0.01) -- + EPE/bad3 (:74-82)."""
+        loss of the continual variant (Stereo_Continual_Adaptation.py:75, weight 0.01; self.proxy_loss, default mean_l1) -- + EPE/bad3 (:74-82)."""
         side = self.sched.SIDE_LOSS and self.wgrad_lanes > 0 and hasattr(r, "lane")
         if not side:
             self._flush_x0(r)
         if self.loss_kind == "proxy":
-            ops.proxy_loss(r, self.pred, self.proxy, self.proxy_ws, self.res_loss, self.dpred if with_grad else None, weight=0.01)
+            ops.proxy_loss(r, self.pred, self.proxy, self.proxy_ws, self.res_loss, self.dpred if with_grad else None, weight=0.01, loss=self.proxy_loss)
         elif side:
             # only the maps + the gradient are on the critical path; the reduction of the loss VALUE and the validation metrics
             # (read by the host after the step) run on a side lane next to the backward pass
@@ -722,12 +723,12 @@ class MadNetEngine(EngineBase, ElisionPasses, BackwardRecorder):
             for nb, (lv, bv) in enumerate(blocks):
                 if do_grad:
                     # loss of the block's prediction: reprojection (Stereo_Online_Adaptation.py:98-107) or, continual
-                    # variant, proxy-label mean_l1 with weight 0.1 (Stereo_Continual_Adaptation.py:100-112)
+                    # variant, the proxy-label loss (self.proxy_loss, default mean_l1) with weight 0.1 (Stereo_Continual_Adaptation.py:100-112)
                     if self.loss_kind == "proxy" and self.rscale != 1:
                         # prediction and labels at 1/s scale, labels / s (:95-112), resized inside the op
-                        ops.proxy_loss_scaled(r, self.disp_k[lv], self.proxy, self.proxy_ws_s, self.res_loss_k, self.rscale, self.ddisp_k, weight=0.1)
+                        ops.proxy_loss_scaled(r, self.disp_k[lv], self.proxy, self.proxy_ws_s, self.res_loss_k, self.rscale, self.ddisp_k, weight=0.1, loss=self.proxy_loss)
                     elif self.loss_kind == "proxy":
-                        ops.proxy_loss(r, self.disp_k[lv], self.proxy, self.proxy_ws, self.res_loss_k, self.ddisp_k, weight=0.1)
+                        ops.proxy_loss(r, self.disp_k[lv], self.proxy, self.proxy_ws, self.res_loss_k, self.ddisp_k, weight=0.1, loss=self.proxy_loss)
                     elif self.rscale != 1:
                         Hs, Ws = self.H0 // self.rscale, self.W0 // self.rscale
                         ops.resize_fwd(r, self.disp_k[lv], self.p_s, Hs, Ws, mul=1.0, mode=0)

@@ -70,8 +70,9 @@ _TABLE = {
     "RESIZE_IMAGE": dict(i="B Hi Wi Cc Ho Wo", p="inp out"),
     "PAD_REFLECT": dict(i="B H W Cc Hp Wp pt pl out_ld", f="div sub", p="inp out"),
     "LOSS": dict(i="B H W phase", f="grad_scale", p="left right disp ws result ddisp"),
-    "PROXY_LOSS": dict(i="B H W", f="weight grad_scale", p="pred proxy ws result dpred"),
-    "PROXY_LOSS_SCALED": dict(i="B H W scale", f="weight grad_scale", p="pred proxy ws result dpred"),
+    # OP_PROXY_LOSS / OP_PROXY_LOSS_SCALED: loss = _ffi.LABEL_LOSS (MH_LOSS_*); 0 = mean_l1 through mh_proxy_loss / mh_proxy_loss_scaled, else mh_label_loss* (rule 0, hi 192)
+    "PROXY_LOSS": dict(i="B H W loss", f="weight grad_scale", p="pred proxy ws result dpred"),
+    "PROXY_LOSS_SCALED": dict(i="B H W scale loss", f="weight grad_scale", p="pred proxy ws result dpred"),
     "SUPERVISED_LOSS": dict(i="B H W", f="weight grad_scale max_disp", p="pred target ws result dpred"),
     "METRICS": dict(i="B H W", f="th", p="disp gt ws result"),
     "METRICS_KITTI": dict(i="B H W", p="disp gt ws result"),

@@ -867,10 +867,44 @@ def reprojection_loss(lib, left, right, disp, ws, result, ddisp=None, grad_scale
         lib.reprojection_loss_phase(_p(left), _p(right), _p(disp), _p(ws), _p(result), _p(ddisp), grad_scale, B, H, W, phase, _p(stream))
 
 
-def proxy_loss(lib, pred, proxy, ws, result, dpred=None, weight=0.01, grad_scale=1.0, stream=None):
-    """result[0] = weight * mean_l1(pred, proxy, valid) (loss_factory.get_proxy_loss); dpred = its gradient (optional)."""
+def _loss_id(loss):
+    """a name of _ffi.LABEL_LOSS or its number -> the number (MH_LOSS_*)"""
+    if isinstance(loss, str):
+        if loss not in _ffi.LABEL_LOSS:
+            raise ValueError("unknown label loss %r, pick one among: %s" % (loss, ", ".join(_ffi.LABEL_LOSS)))
+        return _ffi.LABEL_LOSS[loss]
+    return int(loss)
+
+
+def _record_with_loss(rec, loss, method, *args):
+    """record a PROXY_LOSS / PROXY_LOSS_SCALED op with `loss` in its slot (the recorder's state attribute, put back afterwards)"""
+    before, rec.label_loss = rec.label_loss, loss
+    try:
+        method(*args)
+    finally:
+        rec.label_loss = before
+
+
+def label_loss(lib, pred, label, ws, result, loss, rule, hi, dpred=None, weight=1.0, grad_scale=1.0, stream=None):
+    """result[0] = weight * loss(pred, label, valid) for one of the six names of _ffi.LABEL_LOSS (the reference's scalar (x, y, mask) losses, mh_label_loss);
+    rule 0: valid = !(label <= 0 | label >= hi) (get_proxy_loss), rule 1: valid = !(label == 0 | label >= hi) (get_supervised_loss); result[1] = sum(valid);
+    dpred = its gradient (optional).  Workspace as proxy_loss.  Launched directly, never recorded (a plan carries the proxy rule: proxy_loss(..., loss=))."""
     B, H, W = pred.shape[0], pred.shape[1], pred.shape[2]
-    lib.proxy_loss(_p(pred), _p(proxy), _p(ws), _p(result), _p(dpred), weight, grad_scale, B, H, W, _p(stream))
+    lib.label_loss(_p(pred), _p(label), _p(ws), _p(result), _p(dpred), _loss_id(loss), int(rule), float(hi), weight, grad_scale, B, H, W, _p(stream))
+
+
+def proxy_loss(lib, pred, proxy, ws, result, dpred=None, weight=0.01, grad_scale=1.0, stream=None, loss=0):
+    """result[0] = weight * mean_l1(pred, proxy, valid) (loss_factory.get_proxy_loss); dpred = its gradient (optional).  loss: another name (or number) of
+    _ffi.LABEL_LOSS under the same validity rule -- the same op kind with the number in its `loss` slot when recorded, mh_label_loss when launched."""
+    B, H, W = pred.shape[0], pred.shape[1], pred.shape[2]
+    loss = _loss_id(loss)
+    args = (_p(pred), _p(proxy), _p(ws), _p(result), _p(dpred), weight, grad_scale, B, H, W, _p(stream))
+    if loss == 0:
+        lib.proxy_loss(*args)
+    elif hasattr(lib, "note_refs"):          # a plan.Recorder
+        _record_with_loss(lib, loss, lib.proxy_loss, *args)
+    else:
+        lib.label_loss(*(args[:5] + (loss, 0, 192.0) + args[5:]))
 
 
 def sgm_proxy_ws(lib, B, H, W, D, device, paths=4, median=False, scale=1):
@@ -933,11 +967,19 @@ def colorize(lib, value, out, ws, cmap, out_kind, vmin=None, vmax=None, stream=N
     return out
 
 
-def proxy_loss_scaled(lib, pred, proxy, ws, result, scale, dpred=None, weight=0.1, grad_scale=1.0, stream=None):
+def proxy_loss_scaled(lib, pred, proxy, ws, result, scale, dpred=None, weight=0.1, grad_scale=1.0, stream=None, loss=0):
     """proxy_loss of the prediction and the proxy labels both resized to (H // scale, W // scale), the labels divided by scale (a MAD block's loss under
-    --reprojectionScale, Stereo_Continual_Adaptation.py:95-112) in one op; dpred = its gradient on the full-size grid (optional).  ws: proxy_scaled_ws_floats."""
+    --reprojectionScale, Stereo_Continual_Adaptation.py:95-112) in one op; dpred = its gradient on the full-size grid (optional).  ws: proxy_scaled_ws_floats.
+    loss: as for proxy_loss (mh_label_loss_scaled)."""
     B, H, W = pred.shape[0], pred.shape[1], pred.shape[2]
-    lib.proxy_loss_scaled(_p(pred), _p(proxy), _p(ws), _p(result), _p(dpred), weight, grad_scale, int(scale), B, H, W, _p(stream))
+    loss = _loss_id(loss)
+    args = (_p(pred), _p(proxy), _p(ws), _p(result), _p(dpred), weight, grad_scale, int(scale), B, H, W, _p(stream))
+    if loss == 0:
+        lib.proxy_loss_scaled(*args)
+    elif hasattr(lib, "note_refs"):          # a plan.Recorder
+        _record_with_loss(lib, loss, lib.proxy_loss_scaled, *args)
+    else:
+        lib.label_loss_scaled(*(args[:5] + (loss,) + args[5:]))
 
 
 def supervised_loss(lib, pred, target, ws, result, dpred=None, weight=1.0, grad_scale=1.0, max_disp=192.0, stream=None):

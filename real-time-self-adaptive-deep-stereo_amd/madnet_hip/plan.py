@@ -26,6 +26,7 @@ class Recorder(object):
         self.join_lanes_next = 0  # next op: lane 0 first waits for exactly the side lanes of this bit mask (bit l = lane l)
         self.nodefer = False      # side-lane ops recorded now are launched at once (MH_OP_NODEFER)
         self.wgrad_group_max_m = 0  # grouped filter-gradient launches: pixel cap of this plan's layers (0 = library default)
+        self.label_loss = 0         # the `loss` slot of the PROXY_LOSS / PROXY_LOSS_SCALED ops recorded next (_ffi.LABEL_LOSS; 0 = mean_l1, today's entry points)
         self.work = {}              # op index -> (algorithmic flops, bytes) of the multi-layer ops (a streamed filter-gradient batch)
         self._pending_work = [0.0, 0.0]
         self.cuts = []              # op indices where compile_parts() splits the recording (a collective goes between the parts)
@@ -217,10 +218,10 @@ class Recorder(object):
         self._op(_ffi.OP_LOSS, locals())
 
     def proxy_loss(self, pred, proxy, ws, result, dpred, weight, grad_scale, B, H, W, stream):
-        self._op(_ffi.OP_PROXY_LOSS, locals())
+        self._op(_ffi.OP_PROXY_LOSS, locals(), loss=self.label_loss)
 
     def proxy_loss_scaled(self, pred, proxy, ws, result, dpred, weight, grad_scale, scale, B, H, W, stream):
-        self._op(_ffi.OP_PROXY_LOSS_SCALED, locals())
+        self._op(_ffi.OP_PROXY_LOSS_SCALED, locals(), loss=self.label_loss)
 
     def supervised_loss(self, pred, target, ws, result, dpred, weight, grad_scale, max_disp, B, H, W, stream):
         self._op(_ffi.OP_SUPERVISED_LOSS, locals())
