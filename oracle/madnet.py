@@ -59,12 +59,40 @@ def layer_variables():
     return m
 
 
-def forward(wts, left, right, bulkhead=False, radius_d=2, stride=1, warping=True, want_layers=False):
+class RoundGradBf16(torch.autograd.Function):
+    """Identity forward; the incoming gradient is rounded to bf16 (round to nearest even) in backward.  Placed behind a conv it models
+    "this layer's gradient map is stored in bf16" inside the oracle's own arithmetic (step(bf16_grad_model=True))."""
+
+    @staticmethod
+    def forward(ctx, x):
+        return x.view_as(x)
+
+    @staticmethod
+    def backward(ctx, g):
+        return g.to(torch.bfloat16).to(g.dtype)
+
+
+def _conv_bases(names):
+    """variable names -> the set of conv base names ('model/.../disp-3') they belong to"""
+    return set(n.rsplit("/", 1)[0] for n in names)
+
+
+def forward(wts, left, right, bulkhead=False, radius_d=2, stride=1, warping=True, want_layers=False, dtype=None, round_grad_behind=()):
     """MadNet._preprocess_inputs + _build_network (Nets/MadNet.py:56-66,251-364).
 
     left/right: [B,H,W,3] float (0..255, no normalisation).  Returns the list of 6
-    full-resolution disparities [d6,d5,d4,d3,d2ctx,final] (+ the layer dict)."""
+    full-resolution disparities [d6,d5,d4,d3,d2ctx,final] (+ the layer dict).
+    dtype: None = the tensors' own; torch.float64 = weights, frames and every op in double (the high-precision reference of the tests).
+    round_grad_behind: conv base names whose output gradient is rounded to bf16 on its way back (RoundGradBf16)."""
+    if dtype is not None:
+        wts = {n: (w if w.dtype == dtype else w.to(dtype)) for n, w in wts.items()}
+        left, right = left.to(dtype), right.to(dtype)
     dt = left.dtype
+    rgb = set(round_grad_behind)
+
+    def conv(x, base, **kw):
+        y = T.conv2d(x, wts[base + "weights"], wts[base + "biases"], **kw)
+        return RoundGradBf16.apply(y) if base[:-1] in rgb else y
     H0, W0 = left.shape[1], left.shape[2]
     L = T.pad_image(left, 64)
     R = T.pad_image(right, 64)
@@ -74,9 +102,7 @@ def forward(wts, left, right, bulkhead=False, radius_d=2, stride=1, warping=True
     def pyramid(x, prefix):
         feats = []
         for i, (_, _, s) in enumerate(PYR_CH):
-            w = wts["model/gc-read-pyramid/conv%d/weights" % (i + 1)]
-            b = wts["model/gc-read-pyramid/conv%d/biases" % (i + 1)]
-            x = T.conv2d(x, w, b, stride=s, alpha=0.2)
+            x = conv(x, "model/gc-read-pyramid/conv%d/" % (i + 1), stride=s, alpha=0.2)
             layers["%s/conv%d" % (prefix, i + 1)] = x
             feats.append(x)
         return feats
@@ -92,7 +118,7 @@ def forward(wts, left, right, bulkhead=False, radius_d=2, stride=1, warping=True
         x = volume
         for j in range(6):
             base = "model/G%d/fgc-volume-filtering-%d/disp-%d/" % (k, k, j + 1)
-            x = T.conv2d(x, wts[base + "weights"], wts[base + "biases"], alpha=(0.2 if j < 5 else 1.0))
+            x = conv(x, base, alpha=(0.2 if j < 5 else 1.0))
             layers["fgc-volume-filtering-%d/disp%d" % (k, j + 1)] = x
         return x
 
@@ -118,8 +144,7 @@ def forward(wts, left, right, bulkhead=False, radius_d=2, stride=1, warping=True
     x = torch.cat([fl[3], V2_init], dim=-1)                           # MadNet.py:123
     for j, (_, rate) in enumerate(CTX):
         base = "model/context-%d/" % (j + 1)
-        x = T.conv2d(x, wts[base + "weights"], wts[base + "biases"], dilation=rate,
-                     alpha=(0.2 if j < 6 else 1.0))
+        x = conv(x, base, dilation=rate, alpha=(0.2 if j < 6 else 1.0))
         layers["context%d" % (j + 1)] = x
     final_disp = V2_init + x                                          # MadNet.py:168
     layers["final_disp"] = final_disp
@@ -141,43 +166,71 @@ def momentum_update(wts, accum, grads, lr, momentum=0.9):
             wts[name].sub_(lr * accum[name])
 
 
+def _block_loss(p, left, right, loss, proxy, reprojection_scale):
+    """Loss of ONE block's prediction p (Stereo_Online_Adaptation.py:91-107; continual variant Stereo_Continual_Adaptation.py:100-112)."""
+    mult = float(left.shape[1] // p.shape[1])                 # Stereo_Online_Adaptation.py:102-103
+    # inputs_modules = scale_tensor(., reprojectionScale) (Stereo_Online_Adaptation.py:22-23,91-95); `mult` stays the ratio to
+    # the UNSCALED frame (:102), i.e. 1 for the full-resolution predictions
+    s = int(reprojection_scale)
+    ls = T.resize_bilinear(left, left.shape[1] // s, left.shape[2] // s) if s != 1 else left
+    rs = T.resize_bilinear(right, right.shape[1] // s, right.shape[2] // s) if s != 1 else right
+    p = T.resize_bilinear(p, ls.shape[1], ls.shape[2]) * mult
+    return T.reprojection_loss(p, ls, rs) if loss == "reprojection" else T.proxy_loss(p, proxy, 0.1)
+
+
 def step(wts, accum, left, right, gt, mode="FULL", block_vars=None, block_index=None,
-         lr=1e-4, radius_d=2, stride=1, loss="reprojection", proxy=None, reprojection_scale=1, warping=True, adam=None):
+         lr=1e-4, radius_d=2, stride=1, loss="reprojection", proxy=None, reprojection_scale=1, warping=True, adam=None,
+         blocks=None, dtype=None, bf16_grad_model=False):
     """One iteration of the loop body Stereo_Online_Adaptation.py:178-253 (device part):
     ONE forward with pre-update weights, full-res loss + EPE/bad3, the selected
     backward and the momentum update.  mode in NONE/FULL/MAD.  For MAD, block_index is
     the sampled block (prediction index) and block_vars its variable-name list.
+    blocks = [(block_index, block_vars), ...]: --numBlocks > 1 (Stereo_Online_Adaptation.py:98-118,181-208): every sampled block's loss and its gradient
+    w.r.t. that block's variables come from the SAME forward pass (the train ops of one session.run all read the pre-update weights), then each block's
+    momentum update; `grads` is the union.  Momentum only.
+    dtype = torch.float64: weights, frames and every op of the forward / backward in double (the gradients come back in double; the update is applied to the
+    caller's tensors in their own type).
+    bf16_grad_model: the gradient behind every conv of the trained block(s) is rounded to bf16 on its way back (RoundGradBf16) -- the oracle's own model of
+    "gradient maps stored in bf16", used to derive the bound of the 'mixed' gradient tests.
     adam = {"m": {...}, "v": {...}, "state": [beta1_power, beta2_power]}: the live demo's optimizer instead of momentum
     (Demo/demo_model.py:164 tf.train.AdamOptimizer(lr); one optimizer object serves all of the demo's train ops (:121-142),
     so the slots are per variable and the ONE pair of beta powers advances with every executed train op)."""
     names = list(wts.keys())
+    if blocks is not None:
+        if mode != "MAD" or block_vars is not None or block_index is not None or adam is not None:
+            raise ValueError("blocks= is the MAD step with momentum; it replaces block_index= / block_vars=")
+    elif mode == "MAD":
+        blocks = [(block_index, block_vars)]
+    if dtype is not None:
+        cw = {n: wts[n].detach().to(dtype) for n in names}
+        left, right, gt = left.to(dtype), right.to(dtype), gt.to(dtype)
+        proxy = proxy.to(dtype) if proxy is not None else None
+    else:
+        cw = wts
     for n in names:
-        wts[n].requires_grad_(mode != "NONE")
+        cw[n].requires_grad_(mode != "NONE")
     bulk = (mode == "MAD")
-    disps = forward(wts, left, right, bulkhead=bulk, radius_d=radius_d, stride=stride, warping=warping)
+    rgb = _conv_bases(sum((list(bv) for _, bv in blocks), [])) if (bf16_grad_model and mode == "MAD") else ()
+    disps = forward(cw, left, right, bulkhead=bulk, radius_d=radius_d, stride=stride, warping=warping, round_grad_behind=rgb)
     # loss="proxy": the continual-adaptation variant (Stereo_Continual_Adaptation.py:75,112): mean_l1 against proxy labels,
     # weight 0.01 on the full-resolution loss, 0.1 on a MAD block's loss
     full_loss = T.reprojection_loss(disps[-1], left, right) if loss == "reprojection" else T.proxy_loss(disps[-1], proxy, 0.01)
     epe, bad3 = T.validation_metrics(disps[-1].detach(), gt)
     grads = {}
     if mode == "FULL":
-        gl = torch.autograd.grad(full_loss, [wts[n] for n in names], allow_unused=True)
+        gl = torch.autograd.grad(full_loss, [cw[n] for n in names], allow_unused=True)
         grads = {n: g for n, g in zip(names, gl) if g is not None}
     elif mode == "MAD":
-        p = disps[block_index]
-        mult = float(left.shape[1] // p.shape[1])                 # Stereo_Online_Adaptation.py:102-103
-        # inputs_modules = scale_tensor(., reprojectionScale) (Stereo_Online_Adaptation.py:22-23,91-95); `mult` stays the ratio to
-        # the UNSCALED frame (:102), i.e. 1 for the full-resolution predictions
-        s = int(reprojection_scale)
-        ls = T.resize_bilinear(left, left.shape[1] // s, left.shape[2] // s) if s != 1 else left
-        rs = T.resize_bilinear(right, right.shape[1] // s, right.shape[2] // s) if s != 1 else right
-        p = T.resize_bilinear(p, ls.shape[1], ls.shape[2]) * mult
-        loss_k = T.reprojection_loss(p, ls, rs) if loss == "reprojection" else T.proxy_loss(p, proxy, 0.1)
-        vs = [n for n in block_vars]
-        gl = torch.autograd.grad(loss_k, [wts[n] for n in vs], allow_unused=True)
-        grads = {n: g for n, g in zip(vs, gl) if g is not None}
+        for nb, (bi, bvars) in enumerate(blocks):
+            loss_k = _block_loss(disps[bi], left, right, loss, proxy, reprojection_scale)
+            vs = [n for n in bvars]
+            gl = torch.autograd.grad(loss_k, [cw[n] for n in vs], allow_unused=True, retain_graph=(nb + 1 < len(blocks)))
+            for n, g in zip(vs, gl):
+                if g is not None:
+                    assert n not in grads, "blocks share the variable %s" % n
+                    grads[n] = g
     for n in names:
-        wts[n].requires_grad_(False)
+        cw[n].requires_grad_(False)
     out = {"loss": float(full_loss.detach()), "epe": float(epe), "bad3": float(bad3),
            "disparity": disps[-1].detach(), "grads": {k: v.detach() for k, v in grads.items()}}
     if grads and adam is not None:
@@ -188,7 +241,7 @@ def step(wts, accum, left, right, gt, mode="FULL", block_vars=None, block_index=
             st[0] = float(torch.tensor(st[0], dtype=torch.float32) * torch.tensor(0.9, dtype=torch.float32))
             st[1] = float(torch.tensor(st[1], dtype=torch.float32) * torch.tensor(0.999, dtype=torch.float32))
     elif grads:
-        momentum_update(wts, accum, grads, lr)
+        momentum_update(wts, accum, {n: (g if g.dtype == wts[n].dtype else g.to(wts[n].dtype)) for n, g in grads.items()}, lr)
     return out
 
 

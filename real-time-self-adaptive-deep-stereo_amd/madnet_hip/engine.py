@@ -46,7 +46,12 @@ class MadNetEngine(EngineBase, ElisionPasses, BackwardRecorder):
         self.md, self.cstride = radius_d, stride
         self.D = 2 * radius_d // stride + 1
         self._alloc()
-        self.layers = {L.name: L for L in self._layer_table()}
+        # two layer tables: 'mixed' runs the coarse layers (conv7 .. conv12, the estimators of levels 6 .. 4) in plain bf16 where only the LAST disparity is read
+        # (FULL / NONE plans); a plan in which losses read the maps of single levels (record_forward(make_disps=...): MAD plans, the offline training step)
+        # runs them in the mode's own forward arithmetic.  record_forward picks the table of the plan it records.
+        self._layer_tables = {c: {L.name: L for L in self._layer_table(coarse_bf16=c)} for c in (True, False)}
+        self.layers = self._layer_tables[True]
+        self._bank_store = {}               # (trans, layer, planes) -> fragment bank: the four dicts below name the banks of the plan being recorded
         self._plans = {}
         self._zeros_needed = []
         # filter gradients: atomic-free split reduction (ops.conv2d_wgrad_partial) unless switched off
@@ -202,17 +207,17 @@ class MadNetEngine(EngineBase, ElisionPasses, BackwardRecorder):
         """... for the input gradient (small layers, bf16 backward)"""
         return self.banks_d.get(base)
 
-    def _pyr_code(self, i, fcode=None):
+    def _pyr_code(self, i, fcode=None, coarse_bf16=True):
         """forward precision code of pyramid layer i: in 'mixed' conv7 .. conv12 (1/16 resolution and below) run plain bf16 -- rounding ONE of them
         to bf16 moves the final disparity by 7e-5 (conv7), 6.8e-5 (conv8), 8e-6 (conv9 .. conv12) px, 1.7e-4 px together (per-layer map,
         profiles/r02_precision_map.txt); conv1 .. conv6 (9e-3 .. 9e-4 each) keep split-bf16 / exact fp32.  None = the mode's code."""
-        if self.precision == "mixed" and i >= self.sched.PYR_BF16_FROM:
+        if self.precision == "mixed" and coarse_bf16 and i >= self.sched.PYR_BF16_FROM:
             return 1
         return fcode
 
-    def _layer_table(self):
+    def _layer_table(self, coarse_bf16=True):
         """the net's 3x3 conv layers (Layer) in forward order, from netdef and the allocated buffers: what record_forward launches and _bank_plan asks the
-        library about.  Forward codes: the mode's, except ('mixed') plain bf16 for conv7 .. conv12 (_pyr_code) and the estimators of levels 6 .. 4."""
+        library about.  Forward codes: the mode's, except ('mixed', coarse_bf16) plain bf16 for conv7 .. conv12 (_pyr_code) and the estimators of levels 6 .. 4."""
         B, fv = self.B, self._fv
         fcode = ops.PRECISION_CODES[self.precision][0]
         out = []
@@ -225,12 +230,12 @@ class MadNetEngine(EngineBase, ElisionPasses, BackwardRecorder):
 
         ids = range(1, 13)
         chain([pyr_name(i) for i in ids], ops.View(self.X0, 2 * B, self.Hp, self.Wp, 3, 4), None, [self.F[i] for i in ids], [self.dF[i] for i in ids],
-              [1] * 12, [self._pyr_code(i, fcode) for i in ids], pyramid=True)
+              [1] * 12, [self._pyr_code(i, fcode, coarse_bf16) for i in ids], pyramid=True)
         for k in LEVELS:
             h, w, c = self.fshape[FEAT[k]]
             cin, ld = c + self.D + (0 if k == 6 else 1), self.dsi_ld[k]
             chain([est_name(k, j) for j in range(1, 7)], ops.View(self.dsi[k], B, h, w, cin, ld), ops.View(self.ddsi[k], B, h, w, cin, ld),
-                  self.E[k] + [self.V[k]], self.dE[k] + [self.dV[k]], [1] * 6, [1 if (self.precision == "mixed" and k >= 4) else fcode] * 6)
+                  self.E[k] + [self.V[k]], self.dE[k] + [self.dV[k]], [1] * 6, [1 if (self.precision == "mixed" and coarse_bf16 and k >= 4) else fcode] * 6)
         h, w, c = self.fshape[4]
         chain([ctx_name(j) for j in range(1, 8)], ops.View(self.ctx_in, B, h, w, c + 1, self.ctx_ld), ops.View(self.dctx_in, B, h, w, c + 1, self.ctx_ld),
               self.Cx + [self.final], self.dCx + [self.dfinal], [rate for _, rate in CTX], [fcode] * 7)
@@ -315,12 +320,19 @@ class MadNetEngine(EngineBase, ElisionPasses, BackwardRecorder):
         pending_head = None
         self.images.begin_plan()
         self._stamp(lib, "start")
+        # 'mixed': the disparity of a level is within the forward tolerance only where that level and everything coarser run the mode's own arithmetic
+        # (tests/test_mad_blocks.py: levels 5 and 4 miss 1e-3 px with the coarse layers in plain bf16) -- a plan whose losses read per-level maps gets it on
+        # every layer, whichever levels it names: a block's gradient does not depend on the blocks trained beside it
+        self.layers = self._layer_tables[not make_disps]
         if self.use_bank:
             plan = self._bank_plan()
+            # the banks of THIS plan (a layer's bank image depends on the arithmetic the plan runs it in; every plan packs its own at its head)
+            self.banks, self.banks_d, self.banks32, self.banks32t = {}, {}, {}, {}
             for n, planes, trans in plan:
-                tgt = self._bank_of(trans)
-                if n not in tgt:
-                    tgt[n] = torch.zeros(ops.pack_bytes(self.W_(n), planes, trans) // 4, device=self.dev)
+                key = (trans, n, planes)
+                if key not in self._bank_store:
+                    self._bank_store[key] = torch.zeros(ops.pack_bytes(self.W_(n), planes, trans) // 4, device=self.dev)
+                self._bank_of(trans)[n] = self._bank_store[key]
             # (in line: on a side lane beside the first pyramid layers, which read no bank, it measured no gain -- profiles/r03_experiments.txt; PACK_SIDE
             #  repeats that experiment: the launch on lane 1 beside pad_reflect + conv1 (28 us), joined in front of conv2)
             side_pack = self.sched.PACK_SIDE and hasattr(lib, "lane") and self.wgrad_lanes > 0
@@ -391,7 +403,7 @@ class MadNetEngine(EngineBase, ElisionPasses, BackwardRecorder):
                     Rk = self._fv(self.Rw[k])
                 ops.corr_fwd(lib, Lk, Rk, dsi, self.md, self.cstride, coff=c, u=(None if k == 6 else self.u[k]),
                              copy_left=True, zero_tail=True)
-            # 'mixed': the estimators of the three coarsest levels run plain bf16 in the forward pass too (_layer_table) -- measured
+            # 'mixed', plans that read only the last disparity: the estimators of the three coarsest levels run plain bf16 in the forward pass too (_layer_table) -- measured
             # contribution to the final disparity 8e-6 / 1e-5 / 1.3e-4 px (profiles/r02_precision_map.txt: rounding ONE group's
             # operands to bf16, everything else fp32), against 2.7e-3 px for level 3 and 7e-2 px for level 2, which keep
             # split-bf16 / exact fp32 like the pyramid and the context network
@@ -578,7 +590,7 @@ class MadNetEngine(EngineBase, ElisionPasses, BackwardRecorder):
         return rng[0]
 
     def build_plan(self, mode, lr=1e-4, block_vars=None, block_level=None, grad_scale=1.0, update=True,
-                   blocks=None, part="all", loss_weights=None, max_disp=192.0, optimizer="momentum", momentum=0.9, collective=None, inputs=None):
+                   blocks=None, part="all", loss_weights=None, max_disp=192.0, optimizer="momentum", momentum=0.9, collective=None, inputs=None, make_disps=()):
         """mode: 'NONE' | 'FULL' | 'MAD' | 'TRAIN' (offline training step of Train.py: multi-scale supervised mean_l1 against
         self.gt with loss_weights from full to lowest resolution, every variable, Adam).
         For MAD: blocks = [(level, variable names), ...] (level in
@@ -591,7 +603,9 @@ class MadNetEngine(EngineBase, ElisionPasses, BackwardRecorder):
         optimizer (MH_OP_ALLREDUCE), so the step is one plan / one hipGraph.  FULL: [estimators + context + loss] leaves on a side lane where the pyramid's
         backward pass starts, [pyramid] follows behind it on lane 0; MAD: the block's ranges + the loss tail as one RCCL group.  Pass grad_scale = 1 / world.
         inputs: an ops.InputTable -- the plan's FIRST op fills left / right / gt / proxy from the device tensors the table names when the plan runs (mh_fetch_inputs:
-        frames from a prefetcher's rotating slots without copy launches in front of a captured step); entries the host leaves empty keep the buffers as they are."""
+        frames from a prefetcher's rotating slots without copy launches in front of a captured step); entries the host leaves empty keep the buffers as they are.
+        make_disps (mode 'NONE'): levels whose full-resolution disparity (disp_k) the forward pass also writes; like every plan that reads per-level maps, 'mixed' then
+        runs every layer in the mode's own forward arithmetic (record_forward)."""
         r = Recorder()
         if inputs is not None and part != "update":
             ops.fetch_inputs(r, inputs.ptr, [self.left, self.right, self.gt, self.proxy])
@@ -615,7 +629,7 @@ class MadNetEngine(EngineBase, ElisionPasses, BackwardRecorder):
             with ops.TUNE_LOCK, ops.precision_scope(self.precision):
                 if mode == "TRAIN":
                     return self._build_train_plan(r, lr, grad_scale, update, part, loss_weights, max_disp)
-                return self._build_plan(r, mode, lr, block_vars, block_level, grad_scale, update, blocks, part, optimizer, momentum, collective)
+                return self._build_plan(r, mode, lr, block_vars, block_level, grad_scale, update, blocks, part, optimizer, momentum, collective, tuple(make_disps))
         finally:
             self.wgrad_lanes = lanes
 
@@ -644,7 +658,7 @@ class MadNetEngine(EngineBase, ElisionPasses, BackwardRecorder):
 
     COLLECTIVE_LANE = 4            # the side lane of the shared-model step's first all-reduce (MH_MAX_LANES - 1: no filter-gradient batch uses it)
 
-    def _build_plan(self, r, mode, lr, block_vars, block_level, grad_scale, update, blocks, part, optimizer="momentum", momentum=0.9, collective=None):
+    def _build_plan(self, r, mode, lr, block_vars, block_level, grad_scale, update, blocks, part, optimizer="momentum", momentum=0.9, collective=None, make_disps=()):
         if optimizer not in ("momentum", "adam"):
             raise ValueError("optimizer must be 'momentum' or 'adam'")
         if collective is not None and (part != "all" or mode not in ("FULL", "MAD") or not update):
@@ -661,7 +675,7 @@ class MadNetEngine(EngineBase, ElisionPasses, BackwardRecorder):
         do_upd = update and part in ("all", "update")
         if mode == "NONE":
             if do_grad:
-                self.record_forward(r, need_x0=False)
+                self.record_forward(r, make_disps=make_disps, need_x0=False)
                 self.record_loss_metrics(r, with_grad=False)
         elif mode == "FULL":
             tv = self.all_vars()

@@ -25,15 +25,18 @@ def _make_list(tmp_path, n, H, W):
     return str(p)
 
 
-@pytest.mark.parametrize("mode", ["NONE", "MAD"])
+@pytest.mark.parametrize("mode", ["NONE", "MAD", "MAD2"])
 def test_cli_end_to_end(hip, tmp_path, mode):
+    """MAD2: --mode MAD --numBlocks 2 (two blocks trained per frame, Stereo_Online_Adaptation.py:181-189)"""
+    two = mode == "MAD2"
+    mode = "MAD" if two else mode
     import Stereo_Online_Adaptation as SOA
     lst = _make_list(tmp_path, 3, 96, 160)
     out = tmp_path / ("out_" + mode)
     os.makedirs(out / "disparities")
     argv = ["-l", lst, "-o", str(out), "--weights", "calibrated:1", "--modelName", "MADNet",
             "--blockConfig", os.path.join(PKG, "block_config", "MadNet_full.json"), "--mode", mode,
-            "--sampleMode", "SEQUENTIAL", "--imageShape", "96", "160", "--logDispStep", "1", "--SSIMTh", "10"]
+            "--sampleMode", "SEQUENTIAL", "--imageShape", "96", "160", "--logDispStep", "1", "--SSIMTh", "10"] + (["--numBlocks", "2"] if two else [])
     args = SOA.build_parser().parse_args(argv)
     np.random.seed(0)
     SOA.main(args)
@@ -41,10 +44,14 @@ def test_cli_end_to_end(hip, tmp_path, mode):
     assert stats.startswith("Metrics,cumulative,average\nEPE,") and "FPS," in stats and "#resets,0" in stats
     series = open(out / "series.csv").read().strip().split("\n")
     assert series[0] == "Iteration,Time,EPE,bad3" and len(series) == 4
+    assert all(np.isfinite(float(row.split(",")[2])) for row in series[1:])
+    assert sorted(os.listdir(out / "disparities")) == ["disparity_%d.png" % t for t in range(3)]       # one file per frame, whatever --numBlocks
     from PIL import Image
     d = np.asarray(Image.open(out / "disparities" / "disparity_2.png"))
     assert d.dtype == np.uint16 and d.shape == (96, 160) and d.max() > 0
-    if mode == "MAD":
+    if two:
+        assert "fetch_counter,1,2,2,1,0" in stats          # SEQUENTIAL sampler, two blocks per frame: (0, 1), (1, 2), (2, 3)
+    elif mode == "MAD":
         assert "fetch_counter,1,1,1,0,0" in stats          # SEQUENTIAL sampler over 3 frames
     else:
         # a20 (Stereo_Online_Adaptation.py:246-251, an INT path): the dumped 16-bit PNG is exactly (clip(d, 0, 256) * 256).astype(uint16) of the

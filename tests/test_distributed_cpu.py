@@ -91,7 +91,7 @@ def test_shared_model_allreduce_world2(early):
     assert np.allclose(res[0][3], w_ref.numpy(), rtol=1e-5, atol=1e-7)
 
 
-def _mad_worker(rank, world, port, q):
+def _mad_worker(rank, world, port, q, num_blocks=1):
     for p in (ROOT, PKG):
         if p not in sys.path:
             sys.path.insert(0, p)
@@ -114,7 +114,7 @@ def _mad_worker(rank, world, port, q):
                                               "_lib": lib, "_device": "cpu"})
         cfg = json.load(open(os.path.join(PKG, "block_config", "MadNet_full.json")))
         # SEQUENTIAL sampling: every rank trains the same block on the same step without exchanging the draw
-        ad = Adapter(net, mode="MAD", lr=1e-2, shared_model=True, use_graph=False, block_config=cfg, sample_mode="SEQUENTIAL", num_blocks=1)
+        ad = Adapter(net, mode="MAD", lr=1e-2, shared_model=True, use_graph=False, block_config=cfg, sample_mode="SEQUENTIAL", num_blocks=num_blocks)
         seen = []
         for _ in range(2):
             out = ad.step(l, r, gt[..., 0])
@@ -153,6 +153,36 @@ def test_shared_model_mad_block_is_one_collective_world2():
     assert res[0][2] and res[1][2], "ranks diverged after the shared MAD update"
     assert abs(res[0][3] - res[1][3]) < 1e-9
     for o, c in res[0][4]:          # the reduced block gradient is the same buffer content on both ranks
+        assert np.array_equal(res[0][5][o:o + c], res[1][5][o:o + c]) and np.abs(res[0][5][o:o + c]).max() > 0
+
+
+@pytest.mark.slow
+def test_shared_model_mad_two_blocks_is_one_collective_world2():
+    """--numBlocks 2 in the shared-model mode: the plan of two blocks is cut into its 'grad' and 'update' parts, the ranges of BOTH blocks + the loss tail
+    travel through the staging buffer as ONE all-reduce between them; both ranks train the same two blocks, end with identical weights and hold the same
+    non-zero reduced gradient in every range of the two blocks."""
+    from conftest import _emul_backend
+    _emul_backend()
+    import socket
+    import numpy as np
+    s = socket.socket(); s.bind(("127.0.0.1", 0)); port = s.getsockname()[1]; s.close()
+    ctx = mp.get_context("spawn")
+    q = ctx.Queue()
+    procs = [ctx.Process(target=_mad_worker, args=(r, 2, port, q, 2)) for r in range(2)]
+    for p in procs:
+        p.start()
+    res = sorted([q.get(timeout=900) for _ in procs], key=lambda x: x[0])
+    for p in procs:
+        p.join(timeout=60)
+        assert p.exitcode == 0
+    assert res[0][1] == res[1][1], "ranks trained different blocks"
+    assert [b for b, _ in res[0][1]] == [(0, 1), (1, 2)]                     # SEQUENTIAL, two blocks per step
+    assert all(c == 1 for _, c in res[0][1]), "a MAD shared step must be ONE collective: %r" % (res[0][1],)
+    # blocks 1 and 2 are neighbours in the flat layout (conv7 .. conv10; estimators 5 and 4): their four ranges coalesce into two, each spanning both blocks
+    assert len(res[0][4]) == 2 and all(c > 300000 for _, c in res[0][4]), res[0][4]
+    assert res[0][2] and res[1][2], "ranks diverged after the shared MAD update"
+    assert abs(res[0][3] - res[1][3]) < 1e-9
+    for o, c in res[0][4]:
         assert np.array_equal(res[0][5][o:o + c], res[1][5][o:o + c]) and np.abs(res[0][5][o:o + c]).max() > 0
 
 

@@ -166,3 +166,38 @@ def test_in_graph_collective_single_rank_equals_private_step(hip, mode):
             assert ad.comm is not None and all(len(p) == 1 for p in ad._plans.values()) and ad.collectives_last_step == (2 if mode == "FULL" else 1)
         res.append((net.engine.params.w.clone(), net.engine.params.m.clone(), [o["loss"] for o in outs]))
     assert torch.equal(res[0][0], res[1][0]) and torch.equal(res[0][1], res[1][1]) and res[0][2] == res[1][2]
+
+
+def test_in_graph_collective_single_rank_two_blocks_equals_private_step(hip):
+    """Adapter(num_blocks=2) with the all-reduce recorded in the plan (MH_OP_ALLREDUCE behind each block's backward pass, the loss tail with the FIRST block's
+    ranges only) on a 1-rank communicator: the sum is the identity, so three steps must reproduce the private two-block steps bit for bit -- and the loss is
+    reduced exactly once: loss / world equals the private loss (a tail that travelled with both blocks would come back doubled on two ranks, and a tail that
+    travelled with none would be unreduced)."""
+    import json
+    import Nets
+    from madnet_hip import _ffi, engine as E, synthetic as S
+    from madnet_hip.adapter import Adapter
+    if _ffi.lib().comm_available() == 0:
+        pytest.skip("the library was built without RCCL (mh_comm_available() == 0)")
+    wn = S.calibrated_weights(dict(E.madnet_manifest()), 1)
+    cfg = json.load(open(os.path.join(PKG, "block_config", "MadNet_full.json")))
+    res = []
+    for shared in (False, True):
+        l, r, gt = S.make_pair(H, W)
+        left = torch.from_numpy(l).cuda(); right = torch.from_numpy(r).cuda()
+        net = Nets.get_stereo_net("MADNet", {"left_img": left, "right_img": right, "split_layers": [None], "sequence": True, "train_portion": "BEGIN",
+                                              "bulkhead": True, "weights": wn, "precision": "mixed"})
+        ad = Adapter(net, mode="MAD", block_config=cfg, lr=LR, sample_mode="SEQUENTIAL", num_blocks=2, shared_model=shared, use_graph=True,
+                     in_graph_collective=(True if shared else None))
+        outs = [ad.step(l, r, gt[..., 0]) for _ in range(3)]
+        assert [o["blocks"] for o in outs] == [[0, 1], [1, 2], [2, 3]]
+        if shared:
+            assert ad.comm is not None and ad.world == 1 and all(len(p) == 1 for p in ad._plans.values()) and ad.collectives_last_step == 2
+            # the recorded plan: one all-reduce per block, the four floats of the loss result inside the first one only
+            P = net.engine.params
+            for key, (plan,) in ad._plans.items():
+                ar = [plan.arr[i] for i in range(plan.n) if plan.arr[i].kind == _ffi.OP_ALLREDUCE]
+                assert len(ar) == 2, (key, len(ar))
+        res.append((net.engine.params.w.clone(), net.engine.params.m.clone(), [o["loss"] for o in outs]))
+    assert torch.equal(res[0][0], res[1][0]) and torch.equal(res[0][1], res[1][1])
+    assert res[0][2] == res[1][2]                 # world = 1: loss / world IS the reduced loss, and it is the private loss
