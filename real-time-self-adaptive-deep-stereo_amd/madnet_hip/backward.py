@@ -44,17 +44,11 @@ class BackwardRecorder(object):
         # zero of the gradient ranges (bias gradients and single-split filter gradients accumulate): with ONE filter-gradient lane it goes
         # onto that lane -- everything that touches g runs there, behind it -- and off the critical path
         g_side = self.sched.ONE_FILL and self.wgrad_lanes == 1 and hasattr(lib, "lane")
-        tail_vars = [pyr_name(1) + "/weights", pyr_name(1) + "/biases"]
-        tail_lane = self.sched.TAIL_LANE if (self.sched.TAIL_SPLIT and self.sched.TAIL_LANE and g_side and pyr_tr[1] and pyr_tr[2] and all(v in train_vars for v in tail_vars)) else 0
         if g_side:
             lib.lane = 1
         try:
-            for o, c in P.ranges([v for v in train_vars if not (tail_lane and v in tail_vars)]):
+            for o, c in P.ranges(train_vars):
                 ops.fill(lib, P.g, o, c)
-            if tail_lane:
-                lib.lane = tail_lane
-                for o, c in P.ranges(tail_vars):
-                    ops.fill(lib, P.g, o, c)
         finally:
             if g_side:
                 lib.lane = 0
@@ -96,7 +90,7 @@ class BackwardRecorder(object):
 
         chain_stamped = [False]
 
-        def flush(lane=None, tail=False, on_main=False):
+        def flush(tail=False, on_main=False):
             """Issue the deferred filter gradients as ONE batch on a side lane (one fork edge): they read only
             buffers that nothing later in the step overwrites, so they may run concurrently with everything that
             follows on lane 0 until the reduction joins them.
@@ -107,17 +101,17 @@ class BackwardRecorder(object):
             # (not with early_update: the ranges a batch completes are collected per flush, not per half)
             if (tail and self.sched.TAIL_MAIN and early_update is None and self.wgrad_lanes > 0 and hasattr(lib, "lane") and self.use_stream and self.partial_wgrad
                     and ops._bwd_precision() == 1):
-                streamed = [it for it in pending if ops.wgrad_stream_ok(it[0], it[1], it[2], it[4], it[5]) and it[0].npix >= self.stream_min_pix]
+                streamed = [it for it in pending if ops.wgrad_stream_ok(it[0], it[1], it[2], it[4], it[5])]
                 rest = [it for it in pending if not any(it is q for q in streamed)]
                 if streamed and rest:
                     pending[:] = rest
-                    flush(lane=lane)
+                    flush()
                     pending[:] = streamed
                     flush(on_main=True)
                     return
             side = self.wgrad_lanes > 0 and hasattr(lib, "lane") and not on_main
             if side:
-                lib.lane = lane if lane else 1 + nflush[0] % self.wgrad_lanes
+                lib.lane = 1 + nflush[0] % self.wgrad_lanes
                 lib.nodefer = nflush[0] < self.sched.NODEFER_BATCHES        # the first batches (context network, 1/4-resolution estimator) carry most of the work
             nflush[0] += 1
             try:
@@ -127,7 +121,7 @@ class BackwardRecorder(object):
                 if self.use_stream and self.partial_wgrad and ops._bwd_precision() == 1:
                     items, casts, todo = [], [], []
                     for xv, dzv, dw, db, stride, dil in pending:
-                        if ops.wgrad_stream_ok(xv, dzv, dw, stride, dil) and xv.npix >= self.stream_min_pix:
+                        if ops.wgrad_stream_ok(xv, dzv, dw, stride, dil):
                             items.append((self.images.queue_cast(xv, casts), self.images.queue_cast(dzv, casts), dw, db, dil))
                         else:
                             todo.append((xv, dzv, dw, db, stride, dil))
@@ -178,6 +172,13 @@ class BackwardRecorder(object):
             written.add(("V", k))
             head_done.add(k)
             return True
+
+        def coord_grad_up(k):
+            """the coordinate gradient of level k into the head of level k + 1: u_k = resize(V_{k+1}) * 20/2^k (MadNet.py:274: u_{k} built at level k+1 with scales[k])"""
+            s_up = 2 ** k
+            if not fuse_head(k + 1, du=self.du[k], Hr=self.Hp // s_up, Wr=self.Wp // s_up, mul=20.0 / s_up):
+                ops.resize_bwd(lib, self.du[k], self.V[k + 1], self.dV[k + 1], self.Hp // s_up, self.Wp // s_up,
+                               mul=20.0 / s_up, mode=0, accumulate=acc_flag(("V", k + 1)))
 
         def conv_bwd(xv, base, dzv, dxv, dx_key, x_act, stride=1, dil=1, need_dx=True, trainable=True, below=None):
             """below: the layer whose output gradient dxv is (its filter gradient reads it as dz): the input gradient's epilogue then also
@@ -280,10 +281,7 @@ class BackwardRecorder(object):
                 ops.corr_bwd(lib, g, Lk, Rk, dL, self._half(self.dF[f], True), self.md, self.cstride, coff=c, du=du,
                              acc_l=acc_flag(("F", f, 0)), acc_r=acc_flag(("F", f, 1)), acc_u=False, copy_left=True)
                 if du is not None:
-                    s_up = 2 ** k
-                    if not fuse_head(k + 1, du=self.du[k], Hr=self.Hp // s_up, Wr=self.Wp // s_up, mul=20.0 / s_up):
-                        ops.resize_bwd(lib, self.du[k], self.V[k + 1], self.dV[k + 1], self.Hp // s_up, self.Wp // s_up,
-                                       mul=20.0 / s_up, mode=0, accumulate=acc_flag(("V", k + 1)))
+                    coord_grad_up(k)
             elif self.sched.FUSE_BACK and (("F", f, 1) in written or first_writer):
                 # the level's correlation + concat gradient and the warp gradient in ONE launch (mh_corr_warp_bwd): the gradient w.r.t. the warped
                 # features never goes to memory; the right half of the feature gradient was zeroed by the pass's single fill / holds earlier contributions,
@@ -293,10 +291,7 @@ class BackwardRecorder(object):
                                   self.md, self.cstride, coff=c, acc_l=acc_flag(("F", f, 0)), copy_left=True, acc_img=acc_flag(("F", f, 1)))
                 self._det_flush(lib, self.dF[f][B:], self.det_dF if self.deterministic else None, self.dF_levels)
                 if need_u:
-                    s_up = 2 ** k
-                    if not fuse_head(k + 1, du=self.du[k], Hr=self.Hp // s_up, Wr=self.Wp // s_up, mul=20.0 / s_up):
-                        ops.resize_bwd(lib, self.du[k], self.V[k + 1], self.dV[k + 1], self.Hp // s_up, self.Wp // s_up,
-                                       mul=20.0 / s_up, mode=0, accumulate=acc_flag(("V", k + 1)))
+                    coord_grad_up(k)
             else:
                 Rk = self._fv(self.Rw[k])
                 du = self.du[k] if need_u else None
@@ -311,11 +306,7 @@ class BackwardRecorder(object):
                              du=du, acc_u=True)
                 self._det_flush(lib, self.dF[f][B:], self.det_dF if self.deterministic else None, self.dF_levels)
                 if need_u:
-                    # u_k = resize(V_{k+1}) * 20/2^k   (MadNet.py:274: u_{k} built at level k+1 with scales[k])
-                    s_up = 2 ** k
-                    if not fuse_head(k + 1, du=self.du[k], Hr=self.Hp // s_up, Wr=self.Wp // s_up, mul=20.0 / s_up):
-                        ops.resize_bwd(lib, self.du[k], self.V[k + 1], self.dV[k + 1], self.Hp // s_up, self.Wp // s_up,
-                                       mul=20.0 / s_up, mode=0, accumulate=acc_flag(("V", k + 1)))
+                    coord_grad_up(k)
         # ---- pyramid towers (batch 2B, shared weights) ---------------------------------------------
         # split point of build_plan(part='grad_split'): every gradient of the estimators / the context network is final here (their
         # batches were flushed level by level), the pyramid's come after -- the shared-model step all-reduces the first range while
@@ -352,20 +343,17 @@ class BackwardRecorder(object):
                         ops.fill(lib, self.dF[i - 1][B:], 0, self.dF[i - 1][B:].numel())
                 if pyr_tr[i]:
                     wgrad(xin, self._fv(self.dF[i]), pyr_name(i), stride=PYR[i - 1][2])
-                if (self.sched.TAIL_SPLIT and i == 2) or i in self.sched.PYR_FLUSH_BEFORE:
-                    flush()                 # (TAIL_SPLIT: conv4 .. conv2 beside conv2's input gradient, not behind it)
                 if need_dx:
                     # dF[i-1] is complete after this launch (the cost-volume contributions were written earlier): it is the dz of layer i - 1
                     sh = self._out_shadow(self._fv(self.dF[i - 1]), pyr_name(i - 1)) if (i - 1 > 1) else None       # (conv1's 3-channel input keeps the tiled kernel)
-                    s2acc = accumulate and PYR[i - 1][2] == 2 and self.sched.PLANES_S2_ACC      # (the stride-2 parity-class kernel adds onto earlier contributions)
-                    wbt = self.banks32t.get(pyr_name(i)) if (not accumulate or s2acc) else None       # (stride-2 layers: only those _bank_plan gave a bank)
+                    wbt = self.banks32t.get(pyr_name(i)) if not accumulate else None       # (stride-2 layers: only those _bank_plan gave a bank)
                     dzs = self._fresh_shadow(self._fv(self.dF[i])) if wbt is not None else None
                     mks = self._fresh_shadow(self._fv(self.F[i - 1])) if wbt is not None else None
                     if wbt is not None and dzs is not None and mks is not None and sh is not None:
                         ops.conv2d_planes_bwd(lib, dzs, self.W_(pyr_name(i)), wbt, dx=self._fv(self.dF[i - 1]), dx_shadow=sh, mask_shadow=mks, mask_alpha=ALPHA,
-                                              stride=PYR[i - 1][2], accumulate=accumulate)
+                                              stride=PYR[i - 1][2])
                         if i in self.sched.PYR_FLUSH_AFTER:
-                            flush(lane=(tail_lane if i == 1 else None))
+                            flush()
                         continue
                     ops.conv2d_dgrad(lib, self._fv(self.dF[i]), self.W_(pyr_name(i)), self._fv(self.dF[i - 1]),
                                      stride=PYR[i - 1][2], accumulate=accumulate, mask_ref=self._fv(self.F[i - 1]),
@@ -375,7 +363,7 @@ class BackwardRecorder(object):
                     if i == 1:
                         self._stamp(lib, "chain_end")           # lane 0: the last input gradient is behind us (the tail flush may put work on lane 0 again)
                         chain_stamped[0] = True
-                    flush(lane=(tail_lane if i == 1 else None), tail=(i == 1))
+                    flush(tail=(i == 1))
         flush()
         if not chain_stamped[0]:
             self._stamp(lib, "chain_end")                       # lane 0: the last input gradient is behind us

@@ -265,16 +265,6 @@ class DispNetEngine(EngineBase):
         im.begin_plan()
         if self.use_planes:
             self._record_banks(r, backward)
-        self._grad_zeroed_early = False
-        if backward and self.sched.ZERO_GRADS_EARLY and hasattr(r, "lane"):
-            # the 168 MB zero fill of the flat gradient buffer (21 us at the HBM rate) leaves the main lane: it runs on the filter gradients' side lane
-            # beside the forward pass (nothing touches the gradients before the backward pass, whose first op joins the lane)
-            r.lane = 1
-            try:
-                ops.fill(r, self.params.g, 0, self.params.total)
-            finally:
-                r.lane = 0
-            self._grad_zeroed_early = True
         # DispNet._preprocess_inputs (DispNet.py:59-73): x/255 - 100/255, reflect pad to a multiple of 64
         ops.pad_reflect(r, self.left, self.X0L.t, self.pt, self.pl, div=255.0, sub=100.0 / 255)
         ops.pad_reflect(r, self.right, self.X0R.t, self.pt, self.pl, div=255.0, sub=100.0 / 255)
@@ -388,11 +378,7 @@ class DispNetEngine(EngineBase):
         early_update = (lr, momentum, grad_scale): see self.sched.EARLY_UPDATE; returns the sorted disjoint [first, end) parameter ranges updated here"""
         lib, B, P, im = r, self.B, self.params, self.images
         upd_fresh, upd_done = [], []
-        if getattr(self, "_grad_zeroed_early", False):
-            lib.join_lanes_next = 1 << 1            # (the fill issued on lane 1 at the head of the forward pass)
-            self._grad_zeroed_early = False
-        else:
-            ops.fill(lib, P.g, 0, P.total)
+        ops.fill(lib, P.g, 0, P.total)
         for n in self.nodes.values():
             n.remaining, n.written = n.consumers, False
         for n, _ in heads:

@@ -76,7 +76,6 @@ class MadNetEngine(EngineBase, ElisionPasses, BackwardRecorder):
         # bf16 backward: the filter gradients of the stride-1 3x3 layers run on the streaming kernel (mh_wgrad_stream: one launch per batch,
         # operands from bf16 shadows of the activations / gradient maps); MH_WGRAD_STREAM=0 keeps the tiled kernels
         self.use_stream = precision in ("mixed", "bf16") and os.environ.get("MH_WGRAD_STREAM", "1") != "0"
-        self.stream_min_pix = 0
         # the bf16 shadows (self.images) are written by the epilogue of the kernel that produces the tensor (mh_conv2d_sh) wherever a conv kernel is the producer; the rest
         # (cost-volume buffers, heads, the top pyramid gradient) go through one mh_shadow_cast per batch.  fuse_shadows = False: cast everything
         self.fuse_shadows = True
@@ -263,10 +262,10 @@ class MadNetEngine(EngineBase, ElisionPasses, BackwardRecorder):
                 plan.append((L.name, L.code, 0))
             if bcode != 1 or L.dx is None:
                 continue
-            # input gradient (bf16).  The stride-2 plane kernel runs where it is the first contribution to its target (the layer's input feeds no cost volume) or,
-            # Schedule.PLANES_S2_ACC, adds onto the correlation's gradient; never on a layer whose input is a concat buffer (L.act: the first layer of an estimator /
-            # the context network, padded gradient rows) -- the library has instances for some of those, the step was never measured with them
-            first = L.stride == 1 or (L.pyramid - 1) not in FEAT.values() or self.sched.PLANES_S2_ACC
+            # input gradient (bf16).  The stride-2 plane kernel runs where it is the first contribution to its target (the layer's input feeds no cost volume);
+            # never on a layer whose input is a concat buffer (L.act: the first layer of an estimator / the context network, padded gradient rows) -- the
+            # library has instances for some of those, the step was never measured with them
+            first = L.stride == 1 or (L.pyramid - 1) not in FEAT.values()
             if (self.use_planes and self.sched.PLANES_DGRAD and large and first and L.act
                     and ops.conv2d_planes_bwd_ok(self.lib, L.dx, w, L.dil, stride=L.stride)):
                 plan.append((L.name, 1, 3))
@@ -333,17 +332,7 @@ class MadNetEngine(EngineBase, ElisionPasses, BackwardRecorder):
                 if key not in self._bank_store:
                     self._bank_store[key] = torch.zeros(ops.pack_bytes(self.W_(n), planes, trans) // 4, device=self.dev)
                 self._bank_of(trans)[n] = self._bank_store[key]
-            # (in line: on a side lane beside the first pyramid layers, which read no bank, it measured no gain -- profiles/r03_experiments.txt; PACK_SIDE
-            #  repeats that experiment: the launch on lane 1 beside pad_reflect + conv1 (28 us), joined in front of conv2)
-            side_pack = self.sched.PACK_SIDE and hasattr(lib, "lane") and self.wgrad_lanes > 0
-            if side_pack:
-                lib.lane = 1
-            try:
-                ops.pack_weights(lib, [(self.W_(n), self._bank_of(trans)[n], planes, trans) for n, planes, trans in plan],
-                                 self.dev, r.keep)
-            finally:
-                if side_pack:
-                    lib.lane = 0
+            ops.pack_weights(lib, [(self.W_(n), self._bank_of(trans)[n], planes, trans) for n, planes, trans in plan], self.dev, r.keep)
         image_conv = (self.sched.IMAGE_CONV and hasattr(self.lib, "conv_image_ok") and self.lib.conv_image_ok(PYR[0][0], PYR[0][1], 3, 3, PYR[0][2]) == 1)
         if image_conv:
             # the padded copy: only conv1's filter gradient reads it (need_x0: the plan has a backward pass) -- off the chain, on lane 1 when there is one
@@ -351,7 +340,7 @@ class MadNetEngine(EngineBase, ElisionPasses, BackwardRecorder):
                 # ONE filter-gradient lane + the side reductions of the loss: the padding launch rides on lane 1 in front of those (record_loss_metrics) -- no fork
                 # edge of its own (a fork at the head of the step cost lane 0 most of what the launch gave back: r05_experiments.txt #15), and conv1's filter
                 # gradient runs on that lane, behind it.  Any other lane layout: in line, as before.
-                self._x0_pending = bool(hasattr(lib, "lane") and self.wgrad_lanes == 1 and self.sched.SIDE_LOSS and self.loss_kind != "proxy" and not self.sched.TAIL_SPLIT)
+                self._x0_pending = bool(hasattr(lib, "lane") and self.wgrad_lanes == 1 and self.sched.SIDE_LOSS and self.loss_kind != "proxy")
                 if not self._x0_pending:
                     ops.pad_reflect(lib, self.lr, self.X0, self.pt, self.pl)
         else:
@@ -362,8 +351,6 @@ class MadNetEngine(EngineBase, ElisionPasses, BackwardRecorder):
                 ops.conv_image_fwd(lib, self.lr, self.Hp, self.Wp, self.pt, self.pl, self.W_(L.name), self.b_(L.name), L.o, stride=L.stride, alpha=ALPHA,
                                    shadow=self._out_shadow(L.o, pyr_name(2)))
                 continue
-            if i == 2 and self.use_bank and self.sched.PACK_SIDE and hasattr(lib, "lane") and self.wgrad_lanes > 0:
-                lib.join_lanes_next = 1 << 1                  # conv1 (3 input channels) never has a bank: every later layer waits for the packing
             # F_i is the input of layer i + 1 (stride 1 or 2: both streamed)
             self._conv_fwd(lib, r, L, shadow_consumer=(pyr_name(i + 1) if i < 12 else None))
         for k in LEVELS:
@@ -461,7 +448,7 @@ class MadNetEngine(EngineBase, ElisionPasses, BackwardRecorder):
         `consumer` (a variable base name) is streamed in the plan being recorded."""
         if not (self.use_stream and self.fuse_shadows and self.partial_wgrad and ops._bwd_precision() == 1):
             return None
-        if (consumer + "/weights") not in self._stream_train or v.npix < self.stream_min_pix:
+        if (consumer + "/weights") not in self._stream_train:
             return None
         self.images.mark(v)
         return self.images.shadow(v)
@@ -696,26 +683,7 @@ class MadNetEngine(EngineBase, ElisionPasses, BackwardRecorder):
                         rr.join_lanes_next, rr.lane, rr.nodefer = 0b1110, self.COLLECTIVE_LANE, True
                         collective.allreduce(rr, [(P.g_loss, lo, P.total + 4 - lo)])
                         rr.lane, rr.nodefer = lane0, nd0
-                cut_done = []
-                if (collective is None and eu is None and self.sched.CUT_UPDATE and do_upd and part == "all" and optimizer == "momentum"
-                        and self.wgrad_lanes > 0 and hasattr(r, "lane") and not self.deterministic):      # (the deterministic twin is flushed in front of the optimizer: one update)
-                    P, lo = self.params, self.pyramid_range()[1]
-
-                    def at_cut(rr):                              # noqa: F811
-                        lane0, nd0 = rr.lane, rr.nodefer
-                        variant = os.environ.get("MH_CUT_VARIANT", "lane4")
-                        if variant == "lane0":                   # diagnostic: the update on lane 0 itself behind a join of the filter-gradient lanes
-                            rr.join_lanes_next = 0b1110
-                        elif variant == "lane4_defer":
-                            rr.join_lanes_next, rr.lane, rr.nodefer = 0b1110, self.COLLECTIVE_LANE, False
-                        else:
-                            rr.join_lanes_next, rr.lane, rr.nodefer = 0b1110, self.COLLECTIVE_LANE, True
-                        ops.momentum(rr, P.w[lo:P.total], P.m[lo:P.total], P.g[lo:P.total], lr, momentum, grad_scale, n=P.total - lo)
-                        rr.lane, rr.nodefer = lane0, nd0
-                        cut_done.append((lo, P.total))
                 done = self.record_backward(r, "final", tv, bulkhead=False, early_update=eu, at_cut=at_cut)
-                if cut_done:
-                    done = tuple(done or ()) + tuple(cut_done)
                 if collective is not None:
                     r.join_next = True                      # the pyramid's filter gradients (side lanes) and the first all-reduce (its lane) are behind us
                     collective.allreduce(r, [(self.params.g_loss, 0, self.pyramid_range()[1])])

@@ -8,7 +8,7 @@ other's experiment state, and a plan did not know what it had been recorded with
     dataclasses.replace(eng.sched, TAIL_MAIN=False)                                # a variant for another engine
 
 Defaults = the schedule of the committed bench line; a field whose default comes from the environment reads it when the Schedule is CREATED.
-Every measured claim cites profiles/rNN_experiments.txt."""
+Every measured claim cites profiles/rNN_experiments.txt; a switch whose other setting lost its measurement is deleted, not left off -- that file keeps the numbers."""
 import os
 from dataclasses import dataclass, field
 
@@ -26,9 +26,6 @@ class Schedule(object):
     # (round 6) pyramid layers (1-based) whose STRIDE-2 forward pass runs the stride-2 plane kernel (conv_planes_s2fwd_kernel: split-bf16 from the producer's
     # planes) instead of the exact-fp32 tiled kernel.  conv5 reads conv4's planes (a plane kernel wrote them); conv3 would need conv2's lo plane (one more launch)
     PLANES_S2_FWD: tuple = (5,)
-    # stride-2 input gradients whose target already holds a contribution (conv5 -> the level-2 features) on the accumulating parity-class kernel: measured +6 us per step
-    # (12.4 us against 12.9 us for the launch, 1.3296 / 1.3283 vs 1.3239 / 1.3225 ms for the step: r06_experiments.txt #9) -- off
-    PLANES_S2_ACC: bool = False
     # (round 6) the fused back end of a level (mh_corr_warp_bwd) is the FIRST writer of its level's feature gradient: no zero fill of the 13.9 MB of level
     # feature gradients at the head of the backward pass, no read of the halves it writes (the row-owned kernel gathers -- it never needed zeros to add to)
     FIRST_WRITER: bool = True
@@ -57,29 +54,16 @@ class Schedule(object):
     # FULL momentum steps: every filter-gradient batch is followed by the momentum update of its layers on its own lane, the launch behind the join
     # covers only what is left.  Measured worse together with the tail split (r04 #17)
     EARLY_UPDATE: bool = False
-    # (round 6) FULL momentum steps of a private model: where the pyramid's backward pass starts, the estimators' and the context network's gradients are final -- 73 % of the
-    # parameters, one contiguous range behind the pyramid's -- and their update leaves on a lane of its own (it waits for the filter-gradient lanes, lane 0 walks on);
-    # the launch behind the final join covers the pyramid's range only.  ONE more launch (EARLY_UPDATE: seven), off the step's tail.  Measured +8 us (r6ag): off
-    CUT_UPDATE: bool = False
-    # mh_pack_weights on the side lane beside pad_reflect / conv1: FULL -3 us (noise), but NONE / MAD get a second stream: +55 / +35 us (r04 #19)
-    PACK_SIDE: bool = False
-    # The step's tail (device time stamps, bench.py --stamps, round 4): the last filter-gradient batch (conv4 .. conv1) could only start behind the
-    # LAST input gradient -- conv1's filter gradient reads what conv2's input gradient writes -- so lane 0 sat idle for 91 us behind the chain.
-    # TAIL_SPLIT: the filter gradients of conv4 .. conv2 leave as a batch of their own BEFORE conv2's input gradient is launched (measured worse).
-    TAIL_SPLIT: bool = False
     # The flush behind the last input gradient: the streamed layers of the last batch (conv4 .. conv2) on lane 0 -- idle from there to the join --
     # while the side lane does the image layer (r04 #17)
     TAIL_MAIN: bool = True
     # the pyramid's filter gradients leave for the side lane in batches; a batch is flushed AFTER the input gradient of layer i for i in
-    # PYR_FLUSH_AFTER (9, 5, 1 = four layers per batch) and BEFORE the input gradient of layer i for i in PYR_FLUSH_BEFORE
+    # PYR_FLUSH_AFTER (9, 5, 1 = four layers per batch)
     PYR_FLUSH_AFTER: tuple = (9, 5, 1)
     # the estimators' filter gradients leave as one batch per level in this tuple (level 6 always flushes); a level not named rides with the next batch.
     # Every flush is a fork edge on lane 0 (a 4.5 us gap in front of the level's correlation gradient in the traced graph), yet fewer batches measured
     # SLOWER: (2,3,6) +5 us, (2,6) +17 us, (6,) +190 us per step (r05_experiments.txt #12)
     EST_FLUSH_AFTER: tuple = (2, 3, 4, 5, 6)
-    PYR_FLUSH_BEFORE: tuple = ()
-    # (TAIL_SPLIT) the last batch on a side lane of its own (0 = same lane); its slice of the gradient buffer is zeroed on that lane too
-    TAIL_LANE: int = 2
     # Deterministic test mode: the float atomics of a step (bias gradients; the warp-gradient scatter when the atomic form of
     # mh_corr_warp_bwd runs) accumulate into 64-bit fixed-point twins (mh_deterministic_add) that the plan flushes in front of their readers --
     # two replays of the same step give bit-identical weights.  At most four deterministic engines per process (two ranges each).
@@ -124,8 +108,6 @@ class DispNetSchedule(object):
     # FULL momentum steps: every filter-gradient batch is followed, on its own side lane, by the momentum update of the layers it completes; the launch
     # behind the join covers what is left.  DispNet has 42 M parameters: one update over all of them is 840 MB of traffic at the very end of the step.
     EARLY_UPDATE: bool = field(default_factory=_env_flag("MH_EARLY_UPDATE", "1"))
-    # the gradient buffer's zero fill on the side lane beside the forward pass
-    ZERO_GRADS_EARLY: bool = field(default_factory=lambda: os.environ.get("MH_DN_ZERO_EARLY", "0") != "0")
     # filter gradients leave for a side lane in batches of FLUSH_MIN layers (one lane: 2 -> 3.15 ms, 3 -> 3.23, 4 -> 3.16, 6 -> 3.20, 12 -> 3.33),
     # the batches alternating over SIDE_LANES lanes (r04 sweep at 375x1242: 1 lane 3.21 ms, 2 lanes 3.39, 3 lanes 3.48)
     FLUSH_MIN: int = field(default_factory=lambda: int(os.environ.get("MH_DN_FLUSH_MIN", "2")))

@@ -16,7 +16,7 @@ from madnet_hip import _ffi, ops, engine as E, dispnet_engine as DE      # noqa:
 from madnet_hip.schedule import Schedule, DispNetSchedule                # noqa: E402
 
 FLIPS = ("SIDE_LOSS", "ONE_FILL", "FUSE_BACK", "HEAD_IN_FRONT", "IMAGE_CONV", "EARLY_UPDATE", "USE_PLANES", "FUSE_SPLITS", "PLANES_DGRAD", "SHADOW_DGRAD", "FUSE_HEAD")
-DN_FLIPS = ("EARLY_UPDATE", "PRODUCER_SHADOWS", "PLANES_S2", "ZERO_GRADS_EARLY", "DETERMINISTIC")
+DN_FLIPS = ("EARLY_UPDATE", "PRODUCER_SHADOWS", "PLANES_S2", "DETERMINISTIC")
 
 
 def signature(plans):
