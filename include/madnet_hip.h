@@ -642,6 +642,9 @@ int mh_conv_image_ok(int32_t C, int32_t N, int32_t kh, int32_t kw, int32_t strid
  * left,right: [B,H,W,3] in 0..255;  disp: [B,H,W], any H, W >= 3.  ws: 16-byte aligned workspace of at least
  * mh_loss_ws_floats(B, H, W) floats -- for every accepted shape no call reads or writes behind that many, and nothing
  * in it needs initialising (every partial sum is written by its own workgroup before the final reduction reads it).
+ * Layout: [ 8 B H W + 12 B (H-2) (W-2) floats that held the warp / SSIM maps | L1 partial sums, one per tile | SSIM partial sums, one per tile ].  No kernel has
+ * read or written the first region since the maps moved to LDS; a LOSS record with a smoothness weight (mh_op) keeps that term's partial sums in its first
+ * mh_smoothness_ws_floats() floats.
  * result[0] = loss, result[1] = mean SSIM term, result[2] = mean L1 term.
  * ddisp (may be NULL: forward only) = grad_scale * dLoss/ddisp. */
 int64_t mh_loss_ws_floats(int32_t B, int32_t H, int32_t W);
@@ -655,6 +658,23 @@ int mh_reprojection_loss(const float* left, const float* right, const float* dis
  * phase 1 = warp + SSIM maps + gradient (partial sums stay in ws), phase 2 = the final reduction into result; 0 = both. */
 int mh_reprojection_loss_phase(const float* left, const float* right, const float* disp, float* ws, float* result, float* ddisp,
                                float grad_scale, int32_t B, int32_t H, int32_t W, int32_t phase, void* stream);
+/* ---- the edge-aware smoothness term of the reference's loss table: smoothness(x, y), Losses/loss_factory.py:183-220, key 'smoothness' (additive: the ABI
+ *      version stays).  disp: [B,H,W]; image: [B,H,W,C], C = 3 or 1, in 0..255.  With * = TF's conv2d (cross-correlation, SAME zero padding, stride 1):
+ *        Kx = [[1,0,-1],[2,0,-2],[1,0,-1]]   Ky = [[1,2,-1],[0,0,0],[-1,-2,-1]]        (the -1 top right of Ky is the reference's literal, :198: kept)
+ *        gx = Kx * (disp / 255), gy = Ky * (disp / 255);  ix = sum_c Kx * (image_c / 255), iy likewise (the kernel is concatenated over the channels, :193-195;
+ *        the reduce_mean that follows runs over ONE channel and is the identity)
+ *        S = mean over B H W of |gx| exp(-|ix|) + |gy| exp(-|iy|)
+ *        dS/ddisp = (Kx^T-scatter of sign(gx) exp(-|ix|) + Ky^T-scatter of sign(gy) exp(-|iy|)) / (255 B H W),  sign(0) = 0
+ *   result[3] = weight * S;  result[0] = weight * S (accumulate 0) or += weight * S (accumulate 1: the term joins the loss another op left there);
+ *   result[1], result[2] untouched (no loss op writes result[3]: the slot is this term's in a 4-float loss result).
+ *   ddisp (may be NULL) = (accumulate 0, every element written) or += (accumulate 1) grad_scale * weight * dS/ddisp.
+ * ws: mh_smoothness_ws_floats() floats, one per 16 x 32 tile, nothing to initialise.  Two launches: the tile kernel (LDS only; partial sums + gradient, one
+ * thread per element) and a float64 reduction in fixed order -- no float atomics, two calls give the same bits.  phase: 1 = tile kernel, 2 = reduction, 0 = both.
+ * Any H, W >= 1 (a 1 x 1 map: 0 and a zero gradient).  MH_ERR_ARG, nothing launched: C outside {1, 3}, a null disp / image / ws / result, a non-positive
+ * dimension, phase outside 0 .. 2, B * H * W >= 2^31. */
+int64_t mh_smoothness_ws_floats(int32_t B, int32_t H, int32_t W);
+int mh_smoothness_loss(const float* disp, const float* image, float* ws, float* result, float* ddisp, float weight, float grad_scale, int32_t accumulate,
+                       int32_t B, int32_t H, int32_t W, int32_t C, int32_t phase, void* stream);
 int64_t mh_metrics_ws_floats(int32_t B, int32_t H, int32_t W);
 int mh_metrics(const float* disp, const float* gt, float* ws, float* result, float pixel_th,
                int32_t B, int32_t H, int32_t W, void* stream);
@@ -787,7 +807,7 @@ uint32_t mh_crc32c(const void* data, int64_t n, uint32_t crc);
 /* ---- native plan executor: the host (Python) compiles the network into an array of op
  *      records once; one FFI call replays it (optionally captured into a hipGraph). ------ */
 enum { MH_OP_CONV = 1, MH_OP_WGRAD, MH_OP_CORR_FWD, MH_OP_CORR_BWD, MH_OP_WARP_FWD, MH_OP_WARP_BWD,
-       MH_OP_RESIZE_FWD, MH_OP_RESIZE_BWD, MH_OP_PAD_REFLECT, MH_OP_LOSS, MH_OP_METRICS,
+       MH_OP_RESIZE_FWD, MH_OP_RESIZE_BWD, MH_OP_PAD_REFLECT, MH_OP_LOSS /* i = B H W phase ; f = grad_scale smooth_weight ; p = left right disp ws result ddisp ; smooth_weight != 0: mh_smoothness_loss(disp, left, C 3, accumulate 1, the same grad_scale and phase) follows, its partial sums in the first floats of ws */, MH_OP_METRICS,
        MH_OP_MOMENTUM, MH_OP_COPY_CH, MH_OP_LEAKY_BWD, MH_OP_FILL, MH_OP_BIAS_GRAD,
        MH_OP_WGRAD_PARTIAL, MH_OP_WGRAD_REDUCE, MH_OP_PROXY_LOSS /* i = B H W loss: loss 0 = mh_proxy_loss, else mh_label_loss with that MH_LOSS_*, rule 0, hi 192 */, MH_OP_SUPERVISED_LOSS, MH_OP_ADAM, MH_OP_ADAM_ADVANCE,
        MH_OP_RESIZE_IMAGE, MH_OP_LEVEL_FRONT, MH_OP_RESERVED_25 /* (was: transposed filter banks of the retired LDS-free kernel) */, MH_OP_PACK_W, MH_OP_CORR_WARP_BWD, MH_OP_SHADOW_CAST, MH_OP_WGRAD_STREAM, MH_OP_HEAD_BWD, MH_OP_HEAD_FWD, MH_OP_CONV_PLANES, MH_OP_PLANE_SPLIT, MH_OP_STAMP, MH_OP_CONV_PLANES_BWD, MH_OP_DET_FLUSH, MH_OP_CONV_IMAGE,

@@ -32,6 +32,7 @@ def build_parser():
     parser.add_argument("--imageShape", help="height width the camera frames are rescaled to, -1 to disable", nargs='+', type=int, default=[480, 640])
     parser.add_argument("--cropShape", help="height width the rescaled frames are centre-cropped / padded to, -1 to disable", nargs='+', type=int, default=[320, 512])
     parser.add_argument("--SSIMTh", help="restore the initial network when the loss exceeds this value", type=float, default=0.5)
+    parser.add_argument("--smoothness", help="weight of the reference's edge-aware smoothness term (Losses/loss_factory.py smoothness: disparity gradients weighed by exp(-|image gradient|) of the left frame) added to every reprojection loss of the step; 0 = the reprojection loss alone", type=float, default=0.0)
     parser.add_argument("--cameraConfig", help="json configuration of the frame source", default=None)
     parser.add_argument("--cameraName", help="registered frame source", default="Synthetic", choices=grabber.get_available_camera())
     parser.add_argument("--calibration", help="json calibration of a raw camera pair (madnet_hip/rectify.py): the frames are rectified on the device before rescale and crop; default: the source delivers rectified frames", default=None)
@@ -62,7 +63,7 @@ def main(args):
     dd = demo_model.RealTimeStereo(camera_frames, model_name=args.modelName, weight_path=args.weights, learning_rate=args.lr,
                                    block_config_path=args.blockConfig, image_shape=args.imageShape, crop_shape=args.cropShape,
                                    SSIMTh=args.SSIMTh, mode=args.mode, device=args.device, on_frame=on_frame, max_frames=args.frames,
-                                   reward_as_online=args.rewardAsOnline, allow_missing=not args.strictWeights, calibration=args.calibration)
+                                   reward_as_online=args.rewardAsOnline, allow_missing=not args.strictWeights, calibration=args.calibration, smoothness=args.smoothness)
     gg = grabber.get_camera(args.cameraName, camera_frames, config=args.cameraConfig, framerate=args.framerate)
     print('Threads ready to start')
     gg.start()

@@ -60,11 +60,12 @@ class RealTimeStereo(threading.Thread):
     def __init__(self, camera_buffer, model_name='MADNet', weight_path=None, learning_rate=0.0001,
                  block_config_path='../block_config/MadNet_full.json', image_shape=[480, 640], crop_shape=[None, None],
                  SSIMTh=0.5, mode='MAD', device='cuda', on_frame=None, display=False, max_frames=None, reward_as_online=False,
-                 precision=None, _lib=None, allow_missing=True, calibration=None):
+                 precision=None, _lib=None, allow_missing=True, calibration=None, smoothness=0.0):
         """allow_missing (default True, like the reference demo whose Saver restores the matching names and leaves the rest at their
         initializer, weights_utils.get_var_to_restore_list): a checkpoint that lacks some model variables still loads.
         calibration (dict or JSON path, madnet_hip/rectify.py; default None: the camera delivers rectified frames): the frames are raw views and are
-        rectified on the device right after their upload, in front of rescale and crop."""
+        rectified on the device right after their upload, in front of rescale and crop.
+        smoothness: weight of the edge-aware smoothness term the adapter adds to its reprojection losses (Adapter(smoothness=)); 0 = none."""
         if mode not in ('NONE', 'FULL', 'MAD'):
             raise ValueError('mode must be NONE, FULL or MAD')
         self._camera_buffer = camera_buffer
@@ -84,6 +85,7 @@ class RealTimeStereo(threading.Thread):
         self._precision = precision
         self._lib = _lib
         self._allow_missing = bool(allow_missing)
+        self._smoothness = float(smoothness)
         self._rectifier = None
         if calibration is not None:
             from madnet_hip.rectify import Rectifier
@@ -126,7 +128,7 @@ class RealTimeStereo(threading.Thread):
         # Demo/demo_model.py:144-154: PROBABILITY sampler with one block for MAD, a fixed single op otherwise
         self._adapter = Adapter(self._net, mode=self._mode, block_config=self._train_config, lr=self._learning_rate,
                                 sample_mode='PROBABILITY', num_blocks=1, fixed_id=[0], ssim_th=self._SSIMTh, optimizer='adam',
-                                reset_optimizer=self._weight_path is None, reward_every_step_first=not self._reward_as_online)
+                                reset_optimizer=self._weight_path is None, reward_every_step_first=not self._reward_as_online, smoothness=self._smoothness)
         self._net_shape = (H, W)
         print('Network Ready')
         return True

@@ -70,6 +70,35 @@ class _MaskedL1Fn(torch.autograd.Function):
         return (dp * g)[..., None], None, None, None, None
 
 
+class _SmoothFn(torch.autograd.Function):
+    """mean(|Kx * x/255| exp(-|Kx * y/255|) + |Ky * x/255| exp(-|Ky * y/255|)) (smoothness, loss_factory.py:183-220); gradient w.r.t. x."""
+
+    @staticmethod
+    def forward(ctx, x, y):
+        lib = _lib()
+        B, H, W = x.shape[0], x.shape[1], x.shape[2]
+        d = x.contiguous().float().view(B, H, W)
+        ws = ops.smoothness_ws(lib, B, H, W, x.device)
+        res = torch.zeros(4, device=x.device)
+        dd = torch.empty(B, H, W, device=x.device)
+        ops.smoothness_loss(lib, d, y.contiguous().float(), ws, res, dd, stream=_stream(x))
+        ctx.save_for_backward(dd)
+        ctx.x_shape = x.shape
+        return res[0]
+
+    @staticmethod
+    def backward(ctx, g):
+        (dd,) = ctx.saved_tensors
+        return (dd * g).view(ctx.x_shape), None
+
+
+def smoothness(x, y):
+    """The reference's edge-aware smoothness constraint between a disparity x [B,H,W,1] and an image y [B,H,W,C], C = 3 or 1, in 0..255 (loss_factory.py:183-220,
+    its quirks kept: include/madnet_hip.h, mh_smoothness_loss); differentiable in x.  A function of the module like the reference's, not a name the builders
+    below accept: in the adaptation step the term rides on the reprojection loss (Adapter(smoothness=), --smoothness)."""
+    return _SmoothFn.apply(x, y)
+
+
 ALL_LOSSES = {'mean_SSIM_l1': None}
 LABEL_LOSSES = {'mean_l1': None}           # the base loss Train.py / Stereo_Continual_Adaptation.py request (their --lossType default / hard-coded name)
 

@@ -82,7 +82,7 @@ def main(args):
     predictions = stereo_net.get_disparities()
     adapter = Adapter(stereo_net, mode=args.mode, block_config=train_config, lr=args.lr, sample_mode=args.sampleMode,
                       num_blocks=args.numBlocks, fixed_id=args.fixedID, sample_frequency=args.sampleFrequency,
-                      ssim_th=args.SSIMTh, reprojection_scale=args.reprojectionScale)
+                      ssim_th=args.SSIMTh, reprojection_scale=args.reprojectionScale, smoothness=getattr(args, 'smoothness', 0.0))
     print('Disparity Net Restored?: {}, number of restored variables: {}'.format(True, len(stereo_net.engine.params.manifest)))
 
     epe_accumulator, bad3_accumulator = [], []
@@ -167,6 +167,7 @@ def build_parser():
     parser.add_argument("--summary", help="accepted for compatibility; no TensorBoard summaries are written", action='store_true')
     parser.add_argument("--imageShape", help="height width every frame is centre-cropped / zero-padded to", nargs='+', type=int, default=[320, 1216])
     parser.add_argument("--SSIMTh", help="restore the initial weights when the loss exceeds this value", type=float, default=0.5)
+    parser.add_argument("--smoothness", help="weight of the reference's edge-aware smoothness term (Losses/loss_factory.py smoothness: disparity gradients weighed by exp(-|image gradient|) of the left frame) added to every reprojection loss of the step; 0 = the reprojection loss alone", type=float, default=0.0)
     parser.add_argument("--sampleFrequency", help="draw new portions every K frames", type=int, default=1)
     parser.add_argument("--mode", help="NONE = inference only, FULL = full back-propagation, MAD = modular adaptation", choices=['NONE', 'FULL', 'MAD'], default='MAD')
     parser.add_argument("--allowMissingWeights", help="variables absent from the checkpoint keep Xavier values (the reference's silent behaviour) instead of raising", action='store_true')

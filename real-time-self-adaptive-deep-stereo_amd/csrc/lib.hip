@@ -295,9 +295,17 @@ static int run_op(const mh_op& o, void* s) {
             return mh_resize_image_fwd((const float*)p[0], (float*)p[1], i[0], i[1], i[2], i[3], i[4], i[5], s);
         case MH_OP_PAD_REFLECT:
             return mh_pad_reflect((const float*)p[0], (float*)p[1], i[0], i[1], i[2], i[3], i[4], i[5], i[6], i[7], i[8], o.f[0], o.f[1], s);
-        case MH_OP_LOSS:
-            return mh_reprojection_loss_phase((const float*)p[0], (const float*)p[1], (const float*)p[2], (float*)p[3], (float*)p[4],
-                                              (float*)p[5], o.f[0], i[0], i[1], i[2], i[3], s);
+        case MH_OP_LOSS: {              // f[1] = smooth_weight: 0 (every record made before the slot existed) = the reprojection loss alone
+            const int rc = mh_reprojection_loss_phase((const float*)p[0], (const float*)p[1], (const float*)p[2], (float*)p[3], (float*)p[4],
+                                                      (float*)p[5], o.f[0], i[0], i[1], i[2], i[3], s);
+            if (rc != 0 || o.f[1] == 0.f) return rc;
+            // the smoothness term of the left frame joins result[0] and ddisp; its partial sums go in front of the reprojection loss's own (the region
+            // of the retired maps: mh_loss_ws_floats in the header), so the two final reductions of a phase-2 record read disjoint floats
+            const int64_t n = (int64_t)i[0] * i[1] * i[2], nw = (int64_t)i[0] * (i[1] - 2) * (i[2] - 2);
+            MH_REQUIRE(mh_smoothness_ws_floats(i[0], i[1], i[2]) <= 8 * n + 12 * nw, MH_ERR_ARG, "MH_OP_LOSS: the smoothness partial sums do not fit in front of the loss's");
+            return mh_smoothness_loss((const float*)p[2], (const float*)p[0], (float*)p[3], (float*)p[4], (float*)p[5], o.f[1], o.f[0], 1,
+                                      i[0], i[1], i[2], 3, i[3], s);
+        }
         case MH_OP_METRICS:
             return mh_metrics((const float*)p[0], (const float*)p[1], (float*)p[2], (float*)p[3], o.f[0], i[0], i[1], i[2], s);
         case MH_OP_MOMENTUM:

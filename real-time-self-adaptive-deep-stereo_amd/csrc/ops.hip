@@ -718,6 +718,109 @@ __global__ __launch_bounds__(256) void loss_final_kernel(LossArgs p) {
 }
 
 // ------------------------------------------------------------------------------------------
+// edge-aware smoothness (Losses/loss_factory.py:183-220): S = mean(|Kx * x| exp(-|Kx * y|) + |Ky * x| exp(-|Ky * y|)), x = disp / 255, y = image / 255
+// ------------------------------------------------------------------------------------------
+struct SmoothArgs {
+    const float* disp; const float* image; float* part; float* result; float* ddisp;
+    int B, H, W, C, nblk, accumulate;
+    float weight, grad_scale;
+};
+
+// One launch for the value and the gradient, tiled like loss_tile_kernel (LT_H x LT_W pixels per workgroup, all through LDS):
+//   A  x / 255 and the channel sum of y / 255 at the tile + a 2-pixel halo (outside the image: the zeros of SAME padding, also across the batch);
+//   B  both stencils of both maps at the tile + a 1-pixel halo -> s_x = sign(gx) exp(-|ix|), s_y likewise (outside the image: zero -- no term lives there);
+//      partial sum of |gx| exp(-|ix|) + |gy| exp(-|iy|) over the tile's own pixels;
+//   C  d S / d x[p] = the transposed stencils gathered at p: sum_ij Kx[i][j] s_x(p - (i-1, j-1)) + Ky[i][j] s_y(p - (i-1, j-1)); one thread per element.
+// The reference's sobel_y literal has -1 top right (:198); kept.
+#define SM_HH (LT_H + 4)
+#define SM_HW (LT_W + 4)
+#define SM_WH (LT_H + 2)
+#define SM_WW (LT_W + 2)
+// s: top-left of a 3x3 window in an array of row stride LD -> Kx * s, Ky * s at its centre
+template <int LD> __device__ __forceinline__ void smooth_stencils(const float* s, float& gx, float& gy) {
+    const float a00 = s[0], a01 = s[1], a02 = s[2], a10 = s[LD], a12 = s[LD + 2], a20 = s[2 * LD], a21 = s[2 * LD + 1], a22 = s[2 * LD + 2];
+    gx = (a00 - a02) + 2.f * (a10 - a12) + (a20 - a22);
+    gy = (a00 + 2.f * a01 - a02) - (a20 + 2.f * a21 + a22);
+}
+__global__ __launch_bounds__(256) void smooth_tile_kernel(SmoothArgs p, int tiles_x, int tiles_y) {
+    __shared__ float red[4];
+    __shared__ float s_d[SM_HH * SM_HW];
+    __shared__ float s_i[SM_HH * SM_HW];
+    __shared__ float s_sx[SM_WH * SM_WW];
+    __shared__ float s_sy[SM_WH * SM_WW];
+    const int tid = threadIdx.x;
+    const int tx = blockIdx.x % tiles_x;
+    const int t2 = blockIdx.x / tiles_x;
+    const int ty = t2 % tiles_y, b = t2 / tiles_y;
+    const int y0t = ty * LT_H, x0t = tx * LT_W;
+    // ---- A -------------------------------------------------------------------------------------
+    for (int i = tid; i < SM_HH * SM_HW; i += 256) {
+        const int ly = i / SM_HW, lx = i - ly * SM_HW;
+        const int y = y0t - 2 + ly, x = x0t - 2 + lx;
+        float dv = 0.f, iv = 0.f;
+        if ((unsigned)y < (unsigned)p.H && (unsigned)x < (unsigned)p.W) {
+            const int64_t q = ((int64_t)b * p.H + y) * p.W + x;
+            dv = p.disp[q] / 255.0f;
+            if (p.C == 3) {
+                const float* im = p.image + q * 3;
+                iv = im[0] / 255.0f + im[1] / 255.0f + im[2] / 255.0f;
+            } else {
+                iv = p.image[q] / 255.0f;
+            }
+        }
+        s_d[i] = dv; s_i[i] = iv;
+    }
+    __syncthreads();
+    // ---- B -------------------------------------------------------------------------------------
+    float term = 0.f;
+    for (int i = tid; i < SM_WH * SM_WW; i += 256) {
+        const int ly = i / SM_WW, lx = i - ly * SM_WW;
+        const int y = y0t - 1 + ly, x = x0t - 1 + lx;
+        float sx = 0.f, sy = 0.f;
+        if ((unsigned)y < (unsigned)p.H && (unsigned)x < (unsigned)p.W) {
+            float gx, gy, ix, iy;
+            smooth_stencils<SM_HW>(s_d + ly * SM_HW + lx, gx, gy);
+            smooth_stencils<SM_HW>(s_i + ly * SM_HW + lx, ix, iy);
+            const float wx = expf(-fabsf(ix)), wy = expf(-fabsf(iy));      // the accurate exp: |ix| reaches 24 on 8-bit frames
+            sx = gx > 0.f ? wx : (gx < 0.f ? -wx : 0.f);
+            sy = gy > 0.f ? wy : (gy < 0.f ? -wy : 0.f);
+            if (ly >= 1 && lx >= 1 && ly <= LT_H && lx <= LT_W) term += fabsf(gx) * wx + fabsf(gy) * wy;
+        }
+        s_sx[i] = sx; s_sy[i] = sy;
+    }
+    const float tot = block_sum(term, red);          // (its barriers also publish s_sx / s_sy)
+    if (tid == 0) p.part[blockIdx.x] = tot;
+    if (!p.ddisp) return;
+    // ---- C -------------------------------------------------------------------------------------
+    const float k = p.grad_scale * p.weight / (255.0f * ((float)p.B * (float)p.H * (float)p.W));
+    for (int i = tid; i < LT_H * LT_W; i += 256) {
+        const int iy = i / LT_W, ix = i - iy * LT_W;
+        const int y = y0t + iy, x = x0t + ix;
+        if (y >= p.H || x >= p.W) continue;
+        // s(p - (i-1, j-1)) for i, j = 0 .. 2 = local (iy + 2 - i, ix + 2 - j): the window read back to front
+        const float* ax = s_sx + iy * SM_WW + ix;
+        const float* ay = s_sy + iy * SM_WW + ix;
+        const float g = (ax[2 * SM_WW + 2] - ax[2 * SM_WW]) + 2.f * (ax[SM_WW + 2] - ax[SM_WW]) + (ax[2] - ax[0])
+                      + (ay[2 * SM_WW + 2] + 2.f * ay[2 * SM_WW + 1] - ay[2 * SM_WW]) - (ay[2] + 2.f * ay[1] + ay[0]);
+        const int64_t q = ((int64_t)b * p.H + y) * p.W + x;
+        p.ddisp[q] = p.accumulate ? p.ddisp[q] + k * g : k * g;
+    }
+}
+
+__global__ __launch_bounds__(256) void smooth_final_kernel(SmoothArgs p) {
+    __shared__ double red[256];
+    double a = 0.0;
+    for (int i = threadIdx.x; i < p.nblk; i += 256) a += (double)p.part[i];
+    red[threadIdx.x] = a; __syncthreads();
+    for (int o = 128; o > 0; o >>= 1) { if ((int)threadIdx.x < o) red[threadIdx.x] += red[threadIdx.x + o]; __syncthreads(); }
+    if (threadIdx.x == 0) {
+        const float v = (float)((double)p.weight * (red[0] / ((double)p.B * p.H * p.W)));
+        p.result[3] = v;
+        p.result[0] = p.accumulate ? p.result[0] + v : v;
+    }
+}
+
+// ------------------------------------------------------------------------------------------
 // validation metrics (Stereo_Online_Adaptation.py:74-82)
 // ------------------------------------------------------------------------------------------
 struct MetArgs { const float* disp; const float* gt; float* part; float* result; int64_t total; int nblk; float th; };
@@ -2606,6 +2709,26 @@ extern "C" int mh_reprojection_loss_phase(const float* left, const float* right,
     if (phase != 2) hipLaunchKernelGGL(loss_tile_kernel, dim3((unsigned)ntiles), dim3(256), 0, s, a, tiles_x, tiles_y, ddisp ? 1 : 0);
     if (phase != 1) hipLaunchKernelGGL(loss_final_kernel, dim3(1), dim3(256), 0, s, a);
     return mh_check_launch("reprojection_loss");
+}
+
+// one partial sum per tile of smooth_tile_kernel: the tiling of the reprojection loss
+extern "C" int64_t mh_smoothness_ws_floats(int32_t B, int32_t H, int32_t W) { return loss_tiles(B, H, W); }
+
+extern "C" int mh_smoothness_loss(const float* disp, const float* image, float* ws, float* result, float* ddisp, float weight, float grad_scale,
+                                  int32_t accumulate, int32_t B, int32_t H, int32_t W, int32_t C, int32_t phase, void* stream) {
+    MH_REQUIRE(phase >= 0 && phase <= 2, MH_ERR_ARG, "mh_smoothness_loss: phase must be 0 (all), 1 (tiles: partial sums + gradient) or 2 (final reduction)");
+    MH_REQUIRE(disp && image && ws && result, MH_ERR_ARG, "mh_smoothness_loss: null argument");
+    MH_REQUIRE(B > 0 && H > 0 && W > 0, MH_ERR_ARG, "mh_smoothness_loss: bad dimension");
+    MH_REQUIRE(C == 1 || C == 3, MH_ERR_ARG, "mh_smoothness_loss: the image has 1 or 3 channels");
+    MH_REQUIRE((int64_t)B * H * W < (1ll << 31), MH_ERR_ARG, "mh_smoothness_loss: too many pixels");
+    const int tiles_x = mh_cdiv(W, LT_W), tiles_y = mh_cdiv(H, LT_H);
+    const int64_t ntiles = loss_tiles(B, H, W);
+    MH_REQUIRE(ntiles < (1ll << 31), MH_ERR_ARG, "mh_smoothness_loss: too many tiles");
+    SmoothArgs a{disp, image, ws, result, ddisp, B, H, W, C, (int)ntiles, accumulate ? 1 : 0, weight, grad_scale};
+    hipStream_t s = (hipStream_t)stream;
+    if (phase != 2) hipLaunchKernelGGL(smooth_tile_kernel, dim3((unsigned)ntiles), dim3(256), 0, s, a, tiles_x, tiles_y);
+    if (phase != 1) hipLaunchKernelGGL(smooth_final_kernel, dim3(1), dim3(256), 0, s, a);
+    return mh_check_launch("mh_smoothness_loss");
 }
 
 extern "C" int64_t mh_metrics_ws_floats(int32_t B, int32_t H, int32_t W) { return 3 * nblk((int64_t)B * H * W) + 16; }

@@ -40,6 +40,7 @@ ALLREDUCE_MAX_BUFS = 8         # MH_ALLREDUCE_MAX_BUFS
 FETCH_MAX = 4                  # MH_FETCH_MAX
 # MH_LOSS_*: name -> the `loss` argument of mh_label_loss / mh_label_loss_scaled and the `loss` slot of a PROXY_LOSS / PROXY_LOSS_SCALED record
 LABEL_LOSS = {"mean_l1": 0, "sum_l1": 1, "mean_l2": 2, "sum_l2": 3, "mean_huber": 4, "sum_huber": 5}
+SMOOTH_TILE = (16, 32)         # rows x columns of a tile of mh_smoothness_loss = one float of its workspace (the tile of the reprojection loss)
 
 
 class InputTable(C.Structure):     # mh_input_table
@@ -204,6 +205,8 @@ SIGNATURES = {
     "mh_loss_ws_floats": (_L, [_I, _I, _I]),
     "mh_reprojection_loss": (_I, [_P, _P, _P, _P, _P, _P, _F, _I, _I, _I, _P]),
     "mh_reprojection_loss_phase": (_I, [_P, _P, _P, _P, _P, _P, _F, _I, _I, _I, _I, _P]),
+    "mh_smoothness_ws_floats": (_L, [_I, _I, _I]),
+    "mh_smoothness_loss": (_I, [_P, _P, _P, _P, _P, _F, _F, _I, _I, _I, _I, _I, _I, _P]),
     "mh_metrics_ws_floats": (_L, [_I, _I, _I]),
     "mh_metrics": (_I, [_P, _P, _P, _P, _F, _I, _I, _I, _P]),
     "mh_metrics_kitti_ws_floats": (_L, [_I, _I, _I]),
@@ -239,7 +242,7 @@ SIGNATURES = {
     "mh_event_destroy": (_I, [_P]),
     "mh_stream_sync": (_I, [_P]),
 }
-_NO_STATUS = {"mh_comm_available", "mh_deterministic_overflow", "mh_bias_grad_blocks", "mh_tune_conv_bank_small", "mh_conv_image_ok", "mh_level_front_head_ok", "mh_deterministic_ranges", "mh_planes_kc16", "mh_conv2d_planes_bwd_ok", "mh_stamp_rate_khz", "mh_pack32_bytes", "mh_conv2d_planes_ok", "mh_tune_conv_planes", "mh_tune_wgrad_target_pct", "mh_tune_wgrad_image", "mh_conv2d_takes_shadows", "mh_conv2d_takes_bank", "mh_conv_bank_small_maxpix", "mh_tune_conv_bank_tile", "mh_tune_conv_rows", "mh_last_error", "mh_last_kernel", "mh_tune_conv_bank", "mh_pack_bytes", "mh_abi_version", "mh_tune_conv_patch", "mh_crc32c", "mh_device_count", "mh_loss_ws_floats", "mh_metrics_ws_floats", "mh_proxy_ws_floats", "mh_proxy_scaled_ws_floats", "mh_metrics_kitti_ws_floats", "mh_frame_prepare_ws_floats", "mh_sgm_ws_bytes", "mh_sgm_ws_bytes_ex", "mh_sgm_ws_bytes_scaled", "mh_sgm_speckle_ws_bytes", "mh_colorize_ws_bytes"}
+_NO_STATUS = {"mh_comm_available", "mh_deterministic_overflow", "mh_bias_grad_blocks", "mh_tune_conv_bank_small", "mh_conv_image_ok", "mh_level_front_head_ok", "mh_deterministic_ranges", "mh_planes_kc16", "mh_conv2d_planes_bwd_ok", "mh_stamp_rate_khz", "mh_pack32_bytes", "mh_conv2d_planes_ok", "mh_tune_conv_planes", "mh_tune_wgrad_target_pct", "mh_tune_wgrad_image", "mh_conv2d_takes_shadows", "mh_conv2d_takes_bank", "mh_conv_bank_small_maxpix", "mh_tune_conv_bank_tile", "mh_tune_conv_rows", "mh_last_error", "mh_last_kernel", "mh_tune_conv_bank", "mh_pack_bytes", "mh_abi_version", "mh_tune_conv_patch", "mh_crc32c", "mh_device_count", "mh_loss_ws_floats", "mh_smoothness_ws_floats", "mh_metrics_ws_floats", "mh_proxy_ws_floats", "mh_proxy_scaled_ws_floats", "mh_metrics_kitti_ws_floats", "mh_frame_prepare_ws_floats", "mh_sgm_ws_bytes", "mh_sgm_ws_bytes_ex", "mh_sgm_ws_bytes_scaled", "mh_sgm_speckle_ws_bytes", "mh_colorize_ws_bytes"}
 
 
 class MadnetHipError(RuntimeError):

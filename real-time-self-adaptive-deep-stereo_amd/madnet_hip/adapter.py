@@ -35,13 +35,17 @@ class Adapter(object):
                  num_blocks=1, fixed_id=0, sample_frequency=1, ssim_th=0.5, reprojection_scale=1,
                  use_graph=True, shared_model=False, process_group=None, loss="reprojection", dilation=1, decay=0.99, uf=0.01,
                  optimizer="momentum", reset_optimizer=False, reward_every_step_first=False, early_reduce=None, in_graph_collective=None, fetch_inputs=None,
-                 kitti_metrics=False, proxy_loss="mean_l1"):
+                 kitti_metrics=False, proxy_loss="mean_l1", smoothness=0.0):
         """loss='proxy', dilation, decay, uf: the continual-adaptation variant (Stereo_Continual_Adaptation.py:75-112,
         205-249, 302-304): proxy-label mean_l1 loss, weight update only every `dilation`-th frame, reward update
         sample_distribution = decay * sample_distribution (+ uf * gain on the last trained blocks).
         proxy_loss (loss='proxy' only): which of the reference's six scalar label losses goes on the proxy labels -- mean_l1 (the reference script's), sum_l1,
         mean_l2, sum_l2, mean_huber, sum_huber (_ffi.LABEL_LOSS; Losses/loss_factory.py:28-108) -- in the full-resolution loss and the MAD blocks' losses alike,
         with the weights of mean_l1 (0.01 / 0.1); the reset test against ssim_th and the MAD reward read its value where they read mean_l1's.
+        smoothness (loss='reprojection' only): weight w of the reference's edge-aware smoothness term (Losses/loss_factory.py:183-220) of the prediction and the left
+        frame, added to every reprojection loss of the step -- the full-resolution one and the MAD blocks', at reprojection_scale on the resized prediction and
+        frame like the loss it joins.  The loss that is minimised is the loss that is watched: out['loss'], the reset test against ssim_th and the MAD reward read
+        the sum; out['smoothness'] = w * S of the full-resolution prediction.  0 (default): every plan is what it is without the keyword.
         optimizer='adam', reset_optimizer, reward_every_step_first: the live demo's variant of the loop (Demo/demo_model.py:164,
         203-208, 253-262): tf.train.AdamOptimizer(lr) instead of momentum; a reset without a weight file re-runs the initialisers,
         i.e. also clears the optimizer slots; its `first` flag is never cleared, so every step re-seeds both remembered losses.
@@ -61,6 +65,13 @@ class Adapter(object):
         self.net, self.eng, self.lib = net, net.engine, net._lib
         self.loss, self.dilation, self.decay, self.uf = loss, max(1, int(dilation)), decay, uf
         self.proxy_loss = proxy_loss
+        self.smoothness = float(smoothness)
+        if self.smoothness != 0.0 and loss == "proxy":
+            raise ValueError("smoothness needs loss='reprojection' (the label-loss records carry no image)")
+        if self.smoothness != 0.0 and not hasattr(self.eng, "smoothness"):
+            raise NotImplementedError("the smoothness term needs an engine that records it")
+        if hasattr(self.eng, "smoothness"):
+            self.eng.smoothness = self.smoothness       # (before the first plan is built: the weight is a slot of the LOSS records)
         if loss == "proxy":
             if not hasattr(self.eng, "proxy"):
                 raise NotImplementedError("the proxy-label loss needs an engine with a proxy buffer")
@@ -303,6 +314,7 @@ class Adapter(object):
         self.step_count += 1
         out = {"epe": epe, "bad3": bad3, "loss": new_loss, "disparity": eng.pred,
                "blocks": list(self.blocks_to_train) if self.mode == "MAD" else [], "reset": did_reset}
+        out["smoothness"] = float(self._host[3]) / (self.world if self.shared else 1)      # result[3] of the full-resolution loss: w * S; 0 without the term (no other op writes the slot)
         if self.kitti:
             out["epe_gt0"], out["d1"] = float(self._host[4]), float(self._host[5])
         return out
@@ -310,7 +322,7 @@ class Adapter(object):
 
 class MultiAdapter(object):
     """S stereo streams with PRIVATE models on ONE GPU ("several streams per GPU may be batched"): every stream keeps its own
-    Adapter -- weights, optimizer state, sampler, reward logic, reset, its loss and proxy_loss -- and one step() advances all of them; the S step plans run as parallel
+    Adapter -- weights, optimizer state, sampler, reward logic, reset, its loss, proxy_loss and smoothness weight -- and one step() advances all of them; the S step plans run as parallel
     branches of ONE hipGraph (mh_plans_run), one graph per combination of plan keys (FULL / NONE: one; MAD: the sampled blocks of every stream).
     The models' chains are serial inside their branch (engine.wgrad_lanes = 0, set here before any plan is built)."""
 

@@ -104,6 +104,7 @@ class DispNetEngine(EngineBase):
         self.proxy = z(B, H, W); self.proxy_ws = z(lib.proxy_ws_floats(B, H, W))
         self.loss_kind = "reprojection"
         self.proxy_loss = "mean_l1"       # loss_kind 'proxy': which of _ffi.LABEL_LOSS goes on the labels (Adapter(proxy_loss=))
+        self.smoothness = 0.0             # loss_kind 'reprojection': weight of the edge-aware smoothness term in the LOSS record (Adapter(smoothness=)); 0 = none
         self.loss_ws = z(lib.loss_ws_floats(B, H, W)); self.met_ws = z(lib.metrics_ws_floats(B, H, W))
         self.res_loss = self.params.g_loss[self.params.total:self.params.total + 4]; self.res_met = z(4)   # (loss result behind the gradients: one collective carries both)
         self.ops = []
@@ -353,7 +354,7 @@ class DispNetEngine(EngineBase):
         if self.loss_kind == "proxy":
             ops.proxy_loss(r, self.pred, self.proxy, self.proxy_ws, self.res_loss, self.dpred if with_grad else None, weight=0.01, loss=self.proxy_loss)
         else:
-            ops.reprojection_loss(r, self.left, self.right, self.pred, self.loss_ws, self.res_loss, self.dpred if with_grad else None)
+            ops.reprojection_loss(r, self.left, self.right, self.pred, self.loss_ws, self.res_loss, self.dpred if with_grad else None, smoothness=self.smoothness)
         self.record_metrics(r)
 
     # ---- backward (derived from the op list) ------------------------------------------------------------

@@ -150,6 +150,7 @@ class MadNetEngine(EngineBase, ElisionPasses, BackwardRecorder):
         self.proxy_ws = z(self.lib.proxy_ws_floats(B, self.H0, self.W0))
         self.loss_kind = "reprojection"
         self.proxy_loss = "mean_l1"       # loss_kind 'proxy': which of _ffi.LABEL_LOSS goes on the labels (Adapter(proxy_loss=)); the workspaces serve all six
+        self.smoothness = 0.0             # loss_kind 'reprojection': weight of the edge-aware smoothness term in every LOSS record (Adapter(smoothness=)); 0 = none
         self.rscale = 1
 
     def set_reprojection_scale(self, s):
@@ -498,17 +499,17 @@ class MadNetEngine(EngineBase, ElisionPasses, BackwardRecorder):
             # only the maps + the gradient are on the critical path; the reduction of the loss VALUE and the validation metrics
             # (read by the host after the step) run on a side lane next to the backward pass
             ops.reprojection_loss(r, self.left, self.right, self.pred, self.loss_ws, self.res_loss,
-                                  self.dpred if with_grad else None, phase=1)
+                                  self.dpred if with_grad else None, phase=1, smoothness=self.smoothness)
         else:
             ops.reprojection_loss(r, self.left, self.right, self.pred, self.loss_ws, self.res_loss,
-                                  self.dpred if with_grad else None)
+                                  self.dpred if with_grad else None, smoothness=self.smoothness)
         if side:
             r.lane = 1
             try:
                 self._stamp(r, "side_lane_first_op")
                 self._flush_x0(r)               # (the padded frames: read by conv1's filter gradient only, on this lane, at the far end of the step)
                 if self.loss_kind != "proxy":
-                    ops.reprojection_loss(r, self.left, self.right, self.pred, self.loss_ws, self.res_loss, None, phase=2)
+                    ops.reprojection_loss(r, self.left, self.right, self.pred, self.loss_ws, self.res_loss, None, phase=2, smoothness=self.smoothness)
                 self.record_metrics(r)
             finally:
                 r.lane = 0
@@ -714,11 +715,11 @@ class MadNetEngine(EngineBase, ElisionPasses, BackwardRecorder):
                     elif self.rscale != 1:
                         Hs, Ws = self.H0 // self.rscale, self.W0 // self.rscale
                         ops.resize_fwd(r, self.disp_k[lv], self.p_s, Hs, Ws, mul=1.0, mode=0)
-                        ops.reprojection_loss(r, self.left_s, self.right_s, self.p_s, self.loss_ws_s, self.res_loss_k, self.dp_s)
+                        ops.reprojection_loss(r, self.left_s, self.right_s, self.p_s, self.loss_ws_s, self.res_loss_k, self.dp_s, smoothness=self.smoothness)
                         ops.resize_bwd(r, self.dp_s, self.disp_k[lv], self.ddisp_k, Hs, Ws, mul=1.0, mode=0)
                     else:
                         ops.reprojection_loss(r, self.left, self.right, self.disp_k[lv], self.loss_ws_k, self.res_loss_k,
-                                              self.ddisp_k)
+                                              self.ddisp_k, smoothness=self.smoothness)
                     self.record_backward(r, lv, bv, bulkhead=True)
                 if collective is not None:
                     # the block's gradient ranges + the loss tail (behind the gradient buffer) as ONE RCCL group between the block's backward pass and its update

@@ -69,7 +69,8 @@ _TABLE = {
     "RESIZE_BWD": dict(i="B Hi Wi Hr Wr cy cx Ho Wo mode accumulate", f="mul", p="g inp din"),
     "RESIZE_IMAGE": dict(i="B Hi Wi Cc Ho Wo", p="inp out"),
     "PAD_REFLECT": dict(i="B H W Cc Hp Wp pt pl out_ld", f="div sub", p="inp out"),
-    "LOSS": dict(i="B H W phase", f="grad_scale", p="left right disp ws result ddisp"),
+    # OP_LOSS: smooth_weight != 0 = mh_smoothness_loss(disp, left) follows the reprojection loss and adds its term to result[0] and ddisp (Recorder.smoothness)
+    "LOSS": dict(i="B H W phase", f="grad_scale smooth_weight", p="left right disp ws result ddisp"),
     # OP_PROXY_LOSS / OP_PROXY_LOSS_SCALED: loss = _ffi.LABEL_LOSS (MH_LOSS_*); 0 = mean_l1 through mh_proxy_loss / mh_proxy_loss_scaled, else mh_label_loss* (rule 0, hi 192)
     "PROXY_LOSS": dict(i="B H W loss", f="weight grad_scale", p="pred proxy ws result dpred"),
     "PROXY_LOSS_SCALED": dict(i="B H W scale loss", f="weight grad_scale", p="pred proxy ws result dpred"),

@@ -858,13 +858,40 @@ def bias_grad(lib, dz, db, stream=None):
     lib.bias_grad(_p(dz), dz.ld, dz.npix, dz.C, _p(db), _p(stream))
 
 
-def reprojection_loss(lib, left, right, disp, ws, result, ddisp=None, grad_scale=1.0, stream=None, phase=0):
-    """phase 0 = everything; 1 = warp + SSIM maps + gradient (what the backward pass waits for); 2 = the reduction of the loss value."""
+def smoothness_ws(lib, B, H, W, device):
+    """the workspace of smoothness_loss: one float per tile (mh_smoothness_ws_floats), nothing to initialise"""
+    return torch.empty(int(lib.smoothness_ws_floats(B, H, W)), dtype=torch.float32, device=device)
+
+
+def smoothness_loss(lib, disp, image, ws, result, ddisp=None, weight=1.0, grad_scale=1.0, accumulate=False, stream=None, phase=0):
+    """the reference's edge-aware smoothness(x, y) (Losses/loss_factory.py:183-220; mh_smoothness_loss): disp [B,H,W], image [B,H,W,C] (C = 3 or 1) in 0..255.
+    result [4]: result[3] = weight * S, result[0] = (accumulate: +=) weight * S; ddisp (optional) = (accumulate: +=) grad_scale * weight * dS/ddisp.  Launched
+    directly, never recorded: in a plan the term rides on the LOSS record (reprojection_loss(..., smoothness=))."""
     B, H, W = disp.shape[0], disp.shape[1], disp.shape[2]
-    if phase == 0:
-        lib.reprojection_loss(_p(left), _p(right), _p(disp), _p(ws), _p(result), _p(ddisp), grad_scale, B, H, W, _p(stream))
-    else:
-        lib.reprojection_loss_phase(_p(left), _p(right), _p(disp), _p(ws), _p(result), _p(ddisp), grad_scale, B, H, W, phase, _p(stream))
+    Cc = image.shape[3] if image.dim() == 4 else 1
+    lib.smoothness_loss(_p(disp), _p(image), _p(ws), _p(result), _p(ddisp), float(weight), grad_scale, int(bool(accumulate)), B, H, W, Cc, phase, _p(stream))
+
+
+def reprojection_loss(lib, left, right, disp, ws, result, ddisp=None, grad_scale=1.0, stream=None, phase=0, smoothness=0.0):
+    """phase 0 = everything; 1 = warp + SSIM maps + gradient (what the backward pass waits for); 2 = the reduction of the loss value.
+    smoothness: weight w of the edge-aware smoothness term of (disp, left): result[0] += w * S, result[3] = w * S (result then has 4 floats), ddisp += its
+    gradient, each in the phase that writes the reprojection loss's share.  Recorded: the weight in the LOSS record's `smooth_weight` slot (the recorder's state
+    attribute, put back afterwards); launched: the second call made here, its partial sums in the first floats of ws.  0: nothing more is launched or recorded."""
+    B, H, W = disp.shape[0], disp.shape[1], disp.shape[2]
+    smoothness = float(smoothness)
+    recording = hasattr(lib, "note_refs")          # a plan.Recorder
+    if recording:
+        before, lib.smoothness = lib.smoothness, smoothness
+    try:
+        if phase == 0:
+            lib.reprojection_loss(_p(left), _p(right), _p(disp), _p(ws), _p(result), _p(ddisp), grad_scale, B, H, W, _p(stream))
+        else:
+            lib.reprojection_loss_phase(_p(left), _p(right), _p(disp), _p(ws), _p(result), _p(ddisp), grad_scale, B, H, W, phase, _p(stream))
+    finally:
+        if recording:
+            lib.smoothness = before
+    if smoothness != 0.0 and not recording:
+        lib.smoothness_loss(_p(disp), _p(left), _p(ws), _p(result), _p(ddisp), smoothness, grad_scale, 1, B, H, W, 3, phase, _p(stream))
 
 
 def _loss_id(loss):
