@@ -675,6 +675,32 @@ int mh_reprojection_loss_phase(const float* left, const float* right, const floa
 int64_t mh_smoothness_ws_floats(int32_t B, int32_t H, int32_t W);
 int mh_smoothness_loss(const float* disp, const float* image, float* ws, float* result, float* ddisp, float weight, float grad_scale, int32_t accumulate,
                        int32_t B, int32_t H, int32_t W, int32_t C, int32_t phase, void* stream);
+/* ---- the reprojection loss over the pixels that exist (additive: the ABI version stays): mean_SSIM_l1 of mh_reprojection_loss with its means taken over what
+ *      is valid.  For frames with regions that show nothing -- the wedges device rectification leaves, the zeros of crop_or_pad.  valid_l, valid_r: [B][H][W]
+ *      bytes, non-zero = valid.  With cx = x - disp[p], i0 = clamp(floor(cx), 0, W-1), i1 = clamp(floor(cx) + 1, 0, W-1) (the two taps of the warp):
+ *        v(p) = valid_l[p] != 0 && valid_r[b,y,i0] != 0 && valid_r[b,y,i1] != 0 && isfinite(disp[p]);   a VALID 3x3 window is valid when its nine pixels are
+ *        N1 = #valid pixels, N2 = #valid windows, both over the whole batch
+ *        L1 = sum over valid p, channels c of |rep - left / 256| / (3 N1);   SS = sum over valid windows, c of clip((1 - SSIM) / 2, 0, 1) / (3 N2);   a term whose
+ *        count is 0 is 0
+ *   result[0] = 0.85 SS + 0.15 L1, result[1] = SS, result[2] = L1; result[3] untouched (the smoothness term's slot).
+ *   ddisp (may be NULL) = grad_scale * dLoss/ddisp with v held constant (it is piecewise constant in the disparity); every element written, exactly 0 where v = 0.
+ *   Validity selects, it never multiplies: no value under an invalid pixel (image, warped value, a NaN or Inf disparity) reaches a sum or the gradient.
+ * Three launches: a count pass (one workgroup per 16 x 32 tile, reads disp and the masks, leaves integer counts per tile), the tile kernel of the unmasked loss with
+ * a validity halo in LDS (every workgroup sums the per-tile integers for the scale of the gradient), the float64 reduction.  No float atomics: two calls give the
+ * same bits; with all-ones masks and finite disparities below 2^24 pixels the bits are mh_reprojection_loss_phase's.  phase: 1 = counts + tiles, 2 = reduction, 0 = both.
+ * ws: as mh_reprojection_loss (mh_loss_ws_floats floats, 16-byte aligned).  Its retired map region also carries the masks of a plan (MH_LOSS_MASKED below):
+ *   float offset  T = tiles               : [ smoothness partial sums: T | pad to 4 floats ]              <- mh_loss_valid_offset(B, H, W) = round_up(T, 4)
+ *                                           [ left mask: B H W bytes | pad to 16 bytes ][ right mask: B H W bytes | pad to 16 bytes ][ counts: 2 T int32 ]
+ *   With n = B H W >= 9 and T <= n this ends before float (T + 3) + 2 (n / 4 + 4) + 2 T <= 3.5 n + 11 <= 8 n, inside the region for every H, W >= 3.
+ *   This entry reads its masks from valid_l / valid_r, keeps its counts at that place and never writes the mask bytes of ws.
+ * MH_ERR_ARG, nothing launched: a null mask, the conditions of mh_reprojection_loss (H, W >= 3, the pixel limit, null pointers), a phase outside 0 .. 2;
+ * MH_ERR_ALIGN: a ws that is not 16-byte aligned. */
+int64_t mh_loss_valid_offset(int32_t B, int32_t H, int32_t W);
+int mh_reprojection_loss_masked(const float* left, const float* right, const float* disp, const uint8_t* valid_l, const uint8_t* valid_r,
+                                float* ws, float* result, float* ddisp, float grad_scale, int32_t B, int32_t H, int32_t W, int32_t phase, void* stream);
+/* in the phase slot of a LOSS record (mh_op): phase | MH_LOSS_MASKED runs mh_reprojection_loss_masked with the masks at mh_loss_valid_offset of the record's own ws.
+ * The masks are bytes at fixed addresses: rewriting them between two replays of a captured graph changes the mask without a re-capture. */
+#define MH_LOSS_MASKED 4
 int64_t mh_metrics_ws_floats(int32_t B, int32_t H, int32_t W);
 int mh_metrics(const float* disp, const float* gt, float* ws, float* result, float pixel_th,
                int32_t B, int32_t H, int32_t W, void* stream);
@@ -807,7 +833,7 @@ uint32_t mh_crc32c(const void* data, int64_t n, uint32_t crc);
 /* ---- native plan executor: the host (Python) compiles the network into an array of op
  *      records once; one FFI call replays it (optionally captured into a hipGraph). ------ */
 enum { MH_OP_CONV = 1, MH_OP_WGRAD, MH_OP_CORR_FWD, MH_OP_CORR_BWD, MH_OP_WARP_FWD, MH_OP_WARP_BWD,
-       MH_OP_RESIZE_FWD, MH_OP_RESIZE_BWD, MH_OP_PAD_REFLECT, MH_OP_LOSS /* i = B H W phase ; f = grad_scale smooth_weight ; p = left right disp ws result ddisp ; smooth_weight != 0: mh_smoothness_loss(disp, left, C 3, accumulate 1, the same grad_scale and phase) follows, its partial sums in the first floats of ws */, MH_OP_METRICS,
+       MH_OP_RESIZE_FWD, MH_OP_RESIZE_BWD, MH_OP_PAD_REFLECT, MH_OP_LOSS /* i = B H W phase ; f = grad_scale smooth_weight ; p = left right disp ws result ddisp ; smooth_weight != 0: mh_smoothness_loss(disp, left, C 3, accumulate 1, the same grad_scale and phase) follows, its partial sums in the first floats of ws ; phase | MH_LOSS_MASKED: mh_reprojection_loss_masked, masks in ws */, MH_OP_METRICS,
        MH_OP_MOMENTUM, MH_OP_COPY_CH, MH_OP_LEAKY_BWD, MH_OP_FILL, MH_OP_BIAS_GRAD,
        MH_OP_WGRAD_PARTIAL, MH_OP_WGRAD_REDUCE, MH_OP_PROXY_LOSS /* i = B H W loss: loss 0 = mh_proxy_loss, else mh_label_loss with that MH_LOSS_*, rule 0, hi 192 */, MH_OP_SUPERVISED_LOSS, MH_OP_ADAM, MH_OP_ADAM_ADVANCE,
        MH_OP_RESIZE_IMAGE, MH_OP_LEVEL_FRONT, MH_OP_RESERVED_25 /* (was: transposed filter banks of the retired LDS-free kernel) */, MH_OP_PACK_W, MH_OP_CORR_WARP_BWD, MH_OP_SHADOW_CAST, MH_OP_WGRAD_STREAM, MH_OP_HEAD_BWD, MH_OP_HEAD_FWD, MH_OP_CONV_PLANES, MH_OP_PLANE_SPLIT, MH_OP_STAMP, MH_OP_CONV_PLANES_BWD, MH_OP_DET_FLUSH, MH_OP_CONV_IMAGE,

@@ -36,6 +36,7 @@ def build_parser():
     parser.add_argument("--cameraConfig", help="json configuration of the frame source", default=None)
     parser.add_argument("--cameraName", help="registered frame source", default="Synthetic", choices=grabber.get_available_camera())
     parser.add_argument("--calibration", help="json calibration of a raw camera pair (madnet_hip/rectify.py): the frames are rectified on the device before rescale and crop; default: the source delivers rectified frames", default=None)
+    parser.add_argument("--maskInvalid", help="with --calibration: the reprojection losses run over the pixels that exist only -- not over the wedges rectification leaves, the zeros of the crop's pad, or left pixels whose warp samples the right view's (Rectifier.valid_masks, Adapter(valid_masks=))", action='store_true')
     parser.add_argument("--frames", help="stop after this many frames (default: run until a key is pressed)", type=int, default=None)
     parser.add_argument("--framerate", help="target frames per second of the grabber (0 = as fast as the network takes them)", type=float, default=30)
     parser.add_argument("--output", help="folder for the disparity PNGs (16 bit, value*256)", default=None)
@@ -49,6 +50,8 @@ def main(args):
     assert args.cameraConfig is None or os.path.exists(args.cameraConfig)
     assert args.calibration is None or os.path.exists(args.calibration)
     assert len(args.imageShape) in (1, 2) and len(args.cropShape) in (1, 2)
+    if args.maskInvalid and args.calibration is None:
+        raise SystemExit("--maskInvalid needs --calibration: the masks are the rectification's")
     on_frame = None
     if args.output is not None:
         os.makedirs(args.output, exist_ok=True)
@@ -63,7 +66,8 @@ def main(args):
     dd = demo_model.RealTimeStereo(camera_frames, model_name=args.modelName, weight_path=args.weights, learning_rate=args.lr,
                                    block_config_path=args.blockConfig, image_shape=args.imageShape, crop_shape=args.cropShape,
                                    SSIMTh=args.SSIMTh, mode=args.mode, device=args.device, on_frame=on_frame, max_frames=args.frames,
-                                   reward_as_online=args.rewardAsOnline, allow_missing=not args.strictWeights, calibration=args.calibration, smoothness=args.smoothness)
+                                   reward_as_online=args.rewardAsOnline, allow_missing=not args.strictWeights, calibration=args.calibration, smoothness=args.smoothness,
+                                   mask_invalid=args.maskInvalid)
     gg = grabber.get_camera(args.cameraName, camera_frames, config=args.cameraConfig, framerate=args.framerate)
     print('Threads ready to start')
     gg.start()

@@ -29,29 +29,11 @@ import torch
 import Nets
 from Data_utils import preprocessing
 from madnet_hip.adapter import Adapter
+from madnet_hip.rectify import crop_or_pad           # (defined next to Rectifier.valid_masks, which sends its masks the frames' way)
 
 
 def _disabled(shape):
     return shape is None or shape[0] is None or int(shape[0]) < 0
-
-
-def crop_or_pad(x, th, tw):
-    """tf.image.resize_image_with_crop_or_pad on a [B,h,w,c] device tensor (Demo/demo_model.py:84-86): centre crop with offset
-    (in - target)//2, centre zero pad with (target - in)//2 in front."""
-    h, w = x.shape[1], x.shape[2]
-    if h > th:
-        o = (h - th) // 2
-        x = x[:, o:o + th]
-    if w > tw:
-        o = (w - tw) // 2
-        x = x[:, :, o:o + tw]
-    h, w = x.shape[1], x.shape[2]
-    if h < th or w < tw:
-        out = x.new_zeros(x.shape[0], th, tw, x.shape[3])
-        pt, pl = (th - h) // 2, (tw - w) // 2
-        out[:, pt:pt + h, pl:pl + w] = x
-        x = out
-    return x
 
 
 class RealTimeStereo(threading.Thread):
@@ -60,14 +42,18 @@ class RealTimeStereo(threading.Thread):
     def __init__(self, camera_buffer, model_name='MADNet', weight_path=None, learning_rate=0.0001,
                  block_config_path='../block_config/MadNet_full.json', image_shape=[480, 640], crop_shape=[None, None],
                  SSIMTh=0.5, mode='MAD', device='cuda', on_frame=None, display=False, max_frames=None, reward_as_online=False,
-                 precision=None, _lib=None, allow_missing=True, calibration=None, smoothness=0.0):
+                 precision=None, _lib=None, allow_missing=True, calibration=None, smoothness=0.0, mask_invalid=False):
         """allow_missing (default True, like the reference demo whose Saver restores the matching names and leaves the rest at their
         initializer, weights_utils.get_var_to_restore_list): a checkpoint that lacks some model variables still loads.
         calibration (dict or JSON path, madnet_hip/rectify.py; default None: the camera delivers rectified frames): the frames are raw views and are
         rectified on the device right after their upload, in front of rescale and crop.
-        smoothness: weight of the edge-aware smoothness term the adapter adds to its reprojection losses (Adapter(smoothness=)); 0 = none."""
+        smoothness: weight of the edge-aware smoothness term the adapter adds to its reprojection losses (Adapter(smoothness=)); 0 = none.
+        mask_invalid (needs calibration): the adapter's reprojection losses run over the pixels that exist only (Rectifier.valid_masks sent the frames' way through
+        rescale and crop; Adapter.set_valid_masks) -- the loss that is printed, compared with SSIMTh and rewarded is that one."""
         if mode not in ('NONE', 'FULL', 'MAD'):
             raise ValueError('mode must be NONE, FULL or MAD')
+        if mask_invalid and calibration is None:
+            raise ValueError("mask_invalid needs a calibration: the masks are the rectification's (Rectifier.valid_masks)")
         self._camera_buffer = camera_buffer
         self._model_name = model_name
         self._weight_path = weight_path
@@ -86,6 +72,7 @@ class RealTimeStereo(threading.Thread):
         self._lib = _lib
         self._allow_missing = bool(allow_missing)
         self._smoothness = float(smoothness)
+        self._mask_invalid = bool(mask_invalid)
         self._rectifier = None
         if calibration is not None:
             from madnet_hip.rectify import Rectifier
@@ -129,6 +116,11 @@ class RealTimeStereo(threading.Thread):
         self._adapter = Adapter(self._net, mode=self._mode, block_config=self._train_config, lr=self._learning_rate,
                                 sample_mode='PROBABILITY', num_blocks=1, fixed_id=[0], ssim_th=self._SSIMTh, optimizer='adam',
                                 reset_optimizer=self._weight_path is None, reward_every_step_first=not self._reward_as_online, smoothness=self._smoothness)
+        if self._mask_invalid:
+            vl, vr = self._rectifier.valid_masks(self._image_shape, self._crop_shape)
+            if tuple(vl.shape[1:]) != (H, W):
+                raise ValueError('validity masks of shape {} after rescale / crop, the network was built for {}'.format(tuple(vl.shape[1:]), (H, W)))
+            self._adapter.set_valid_masks(vl, vr)
         self._net_shape = (H, W)
         print('Network Ready')
         return True

@@ -296,15 +296,24 @@ static int run_op(const mh_op& o, void* s) {
         case MH_OP_PAD_REFLECT:
             return mh_pad_reflect((const float*)p[0], (float*)p[1], i[0], i[1], i[2], i[3], i[4], i[5], i[6], i[7], i[8], o.f[0], o.f[1], s);
         case MH_OP_LOSS: {              // f[1] = smooth_weight: 0 (every record made before the slot existed) = the reprojection loss alone
-            const int rc = mh_reprojection_loss_phase((const float*)p[0], (const float*)p[1], (const float*)p[2], (float*)p[3], (float*)p[4],
-                                                      (float*)p[5], o.f[0], i[0], i[1], i[2], i[3], s);
+            const int32_t phase = i[3] & ~MH_LOSS_MASKED;
+            int rc;
+            if ((i[3] & MH_LOSS_MASKED) && i[3] >= 0) {     // the validity masks travel in the record's own workspace (header: mh_reprojection_loss_masked)
+                MH_REQUIRE(p[3] && i[0] > 0 && i[1] >= 3 && i[2] >= 3, MH_ERR_ARG, "MH_OP_LOSS: masked record without a workspace or below 3x3");
+                const uint8_t* vl = (const uint8_t*)((float*)p[3] + mh_loss_valid_offset(i[0], i[1], i[2]));
+                const uint8_t* vr = vl + ((int64_t)i[0] * i[1] * i[2] + 15) / 16 * 16;
+                rc = mh_reprojection_loss_masked((const float*)p[0], (const float*)p[1], (const float*)p[2], vl, vr, (float*)p[3], (float*)p[4], (float*)p[5],
+                                                 o.f[0], i[0], i[1], i[2], phase, s);
+            } else
+                rc = mh_reprojection_loss_phase((const float*)p[0], (const float*)p[1], (const float*)p[2], (float*)p[3], (float*)p[4],
+                                                (float*)p[5], o.f[0], i[0], i[1], i[2], i[3], s);
             if (rc != 0 || o.f[1] == 0.f) return rc;
             // the smoothness term of the left frame joins result[0] and ddisp; its partial sums go in front of the reprojection loss's own (the region
             // of the retired maps: mh_loss_ws_floats in the header), so the two final reductions of a phase-2 record read disjoint floats
             const int64_t n = (int64_t)i[0] * i[1] * i[2], nw = (int64_t)i[0] * (i[1] - 2) * (i[2] - 2);
             MH_REQUIRE(mh_smoothness_ws_floats(i[0], i[1], i[2]) <= 8 * n + 12 * nw, MH_ERR_ARG, "MH_OP_LOSS: the smoothness partial sums do not fit in front of the loss's");
             return mh_smoothness_loss((const float*)p[2], (const float*)p[0], (float*)p[3], (float*)p[4], (float*)p[5], o.f[1], o.f[0], 1,
-                                      i[0], i[1], i[2], 3, i[3], s);
+                                      i[0], i[1], i[2], 3, phase, s);
         }
         case MH_OP_METRICS:
             return mh_metrics((const float*)p[0], (const float*)p[1], (float*)p[2], (float*)p[3], o.f[0], i[0], i[1], i[2], s);

@@ -515,6 +515,9 @@ struct LossArgs {
     int B, H, W, nblk1, nblk2;
     float grad_scale;
 };
+// the masked loss only (a kernel argument of its own, behind the others: LossArgs and the unmasked kernels' argument offsets stay what they were):
+// [B][H][W] masks, non-zero = valid; cnt[tile] = valid pixels, cnt[nblk1 + tile] = valid windows
+struct LossMask { const uint8_t* valid_l; const uint8_t* valid_r; int* cnt; };
 
 __device__ __forceinline__ float block_sum(float v, float* red) {
     v = mh_wave_sum(v);
@@ -541,8 +544,70 @@ __device__ __forceinline__ float block_sum(float v, float* red) {
 #define LT_HW (LT_W + 4)
 #define LT_WH (LT_H + 2)
 #define LT_WW (LT_W + 2)
-__global__ __launch_bounds__(256) void loss_tile_kernel(LossArgs p, int tiles_x, int tiles_y, int with_grad) {
+
+// ---- the masked loss (mh_reprojection_loss_masked): which pixels count ----
+// Byte `idx` of a mask of n >= 4 bytes through its range-checked descriptor (idx = MH_OOB: 0).  The load is the dword that holds the byte; the last dword of a
+// mask whose size is no multiple of 4 is read at n - 4, so no byte behind the mask is touched.
+__device__ __forceinline__ unsigned loss_mask_byte(__amdgpu_buffer_rsrc_t rs, int idx, int n) {
+    const int a = idx == MH_OOB ? MH_OOB : min(idx & ~3, n - 4);
+    const unsigned w = __builtin_amdgcn_raw_buffer_load_b32(rs, a, 0, 0);
+    return (w >> (((unsigned)(idx - a) & 3u) * 8u)) & 0xffu;
+}
+__device__ __forceinline__ bool loss_finite(float v) { return (__builtin_bit_cast(unsigned, v) & 0x7f800000u) != 0x7f800000u; }
+
+// The count pass in front of the masked tile kernel, tiled like it: v(p) = valid_l[p] && valid_r at both taps of the warp && isfinite(disp[p]) on the tile + its
+// halo -> LDS; cnt[tile] = valid pixels of the tile, cnt[nblk1 + tile] = windows whose top-left corner is a pixel of the tile and whose nine pixels are valid.
+// Reads disp and the masks only; integer sums, so the order of the additions cannot change them.
+__global__ __launch_bounds__(256) void loss_count_kernel(LossArgs p, int tiles_x, int tiles_y, LossMask m) {
+    __shared__ unsigned char s_v[LT_HH * LT_HW];
+    __shared__ int s_n[2];
+    const int tid = threadIdx.x;
+    const int tx = blockIdx.x % tiles_x;
+    const int t2 = blockIdx.x / tiles_x;
+    const int ty = t2 % tiles_y, b = t2 / tiles_y;
+    const int y0t = ty * LT_H, x0t = tx * LT_W;
+    const float xmax = (float)(p.W - 1);
+    const int npx = p.B * p.H * p.W;
+    const __amdgpu_buffer_rsrc_t rs_d = mh_make_rsrc(p.disp, (unsigned)npx * 4u);
+    const __amdgpu_buffer_rsrc_t rs_vl = mh_make_rsrc(m.valid_l, (unsigned)npx);
+    const __amdgpu_buffer_rsrc_t rs_vr = mh_make_rsrc(m.valid_r, (unsigned)npx);
+    if (tid < 2) s_n[tid] = 0;
+    for (int i = tid; i < LT_HH * LT_HW; i += 256) {
+        const int ly = i / LT_HW, lx = i - ly * LT_HW;
+        const int y = y0t - 2 + ly, x = x0t - 2 + lx;
+        const bool inb = (unsigned)y < (unsigned)p.H && (unsigned)x < (unsigned)p.W;
+        const int rb = (b * p.H + y) * p.W;
+        const float d = mh_buf_load1(rs_d, inb ? (rb + x) * 4 : MH_OOB);
+        const bool fin = inb && loss_finite(d);
+        const float xf0 = floorf((float)x - d);
+        const int i0 = (int)clampf(xf0, 0.f, xmax), i1 = (int)clampf(xf0 + 1.0f, 0.f, xmax);
+        const unsigned ml = loss_mask_byte(rs_vl, inb ? rb + x : MH_OOB, npx);
+        const unsigned m0 = loss_mask_byte(rs_vr, fin ? rb + i0 : MH_OOB, npx), m1 = loss_mask_byte(rs_vr, fin ? rb + i1 : MH_OOB, npx);
+        s_v[i] = (ml != 0u && m0 != 0u && m1 != 0u) ? 1 : 0;
+    }
+    __syncthreads();
+    const int Hw = p.H - 2, Ww = p.W - 2;
+    int n1 = 0, n2 = 0;
+    for (int i = tid; i < LT_H * LT_W; i += 256) {
+        const int iy = i / LT_W, ix = i - iy * LT_W;
+        const unsigned char* c = s_v + (iy + 2) * LT_HW + ix + 2;         // (pixels outside the image hold 0)
+        n1 += c[0];
+        if (y0t + iy < Hw && x0t + ix < Ww)
+            n2 += c[0] & c[1] & c[2] & c[LT_HW] & c[LT_HW + 1] & c[LT_HW + 2] & c[2 * LT_HW] & c[2 * LT_HW + 1] & c[2 * LT_HW + 2];
+    }
+    if (n1) atomicAdd(s_n + 0, n1);
+    if (n2) atomicAdd(s_n + 1, n2);
+    __syncthreads();
+    if (tid == 0) { m.cnt[blockIdx.x] = s_n[0]; m.cnt[p.nblk1 + blockIdx.x] = s_n[1]; }
+}
+
+// MASKED (mh_reprojection_loss_masked): a pixel that is not valid (loss_count_kernel's v) puts zeros into the LDS maps and nothing into the sums or the gradient --
+// selected, never multiplied, so a NaN under it stays out; a window counts when its nine pixels do; the means run over the counts of loss_count_kernel.
+template <bool MASKED>
+__global__ __launch_bounds__(256) void loss_tile_kernel(LossArgs p, int tiles_x, int tiles_y, int with_grad, LossMask m) {
     __shared__ float red[4];
+    __shared__ unsigned char s_v[MASKED ? LT_HH * LT_HW : 1];
+    __shared__ int s_n[2];
     __shared__ float s_rep[LT_HH * LT_HW * 3];
     __shared__ float s_y[LT_HH * LT_HW * 3];
     __shared__ float s_drep[LT_H * LT_W * 3];
@@ -554,6 +619,14 @@ __global__ __launch_bounds__(256) void loss_tile_kernel(LossArgs p, int tiles_x,
     const int y0t = ty * LT_H, x0t = tx * LT_W;
     const float s = 1.0f / 256.0f;
     const float xmax = (float)(p.W - 1);
+    if (MASKED && with_grad) {          // the counts of the whole batch, for the scale of the gradient: every workgroup sums the per-tile integers (L2 hits)
+        if (tid < 2) s_n[tid] = 0;
+        __syncthreads();
+        int n1 = 0, n2 = 0;
+        for (int i = tid; i < p.nblk1; i += 256) { n1 += m.cnt[i]; n2 += m.cnt[p.nblk1 + i]; }
+        if (n1) atomicAdd(s_n + 0, n1);
+        if (n2) atomicAdd(s_n + 1, n2);                                   // (published by the barriers of phases A and B)
+    }
     // ---- A -------------------------------------------------------------------------------------
     // Round 5: the three halo pixels of a thread go through the phase TOGETHER -- three disparity loads in flight, then all 27 image loads (range-checked buffer
     // loads: a pixel outside the image = an out-of-range offset = zeros, no branch around a load).  The loop this replaces waited for disp, then for its nine
@@ -565,6 +638,9 @@ __global__ __launch_bounds__(256) void loss_tile_kernel(LossArgs p, int tiles_x,
         const __amdgpu_buffer_rsrc_t rs_d = mh_make_rsrc(p.disp, npx * 4u);
         const __amdgpu_buffer_rsrc_t rs_l = mh_make_rsrc(p.left, npx * 12u);
         const __amdgpu_buffer_rsrc_t rs_r = mh_make_rsrc(p.right, npx * 12u);
+        const __amdgpu_buffer_rsrc_t rs_vl = mh_make_rsrc(m.valid_l, MASKED ? npx : 0u);
+        const __amdgpu_buffer_rsrc_t rs_vr = mh_make_rsrc(m.valid_r, MASKED ? npx : 0u);
+        unsigned mv[NI];
         int qv[NI], rbv[NI];
         bool inb[NI];
         float dv[NI];
@@ -590,6 +666,12 @@ __global__ __launch_bounds__(256) void loss_tile_kernel(LossArgs p, int tiles_x,
             const int i0 = (int)clampf(xf0, 0.f, xmax), i1 = (int)clampf(xf1, 0.f, xmax);
             int o0 = (rbv[u] + i0) * 12, o1 = (rbv[u] + i1) * 12, ol = qv[u] * 12;
             MH_KEEP_VGPR(o0); MH_KEEP_VGPR(o1); MH_KEEP_VGPR(ol);
+            if (MASKED) {                   // loss_count_kernel's v, from the same taps
+                const bool fin = inb[u] && loss_finite(dv[u]);
+                const unsigned ml = loss_mask_byte(rs_vl, inb[u] ? qv[u] : MH_OOB, (int)npx);
+                const unsigned m0 = loss_mask_byte(rs_vr, fin ? rbv[u] + i0 : MH_OOB, (int)npx), m1 = loss_mask_byte(rs_vr, fin ? rbv[u] + i1 : MH_OOB, (int)npx);
+                mv[u] = (ml != 0u && m0 != 0u && m1 != 0u) ? 1u : 0u;
+            }
 #pragma unroll
             for (int c = 0; c < 3; ++c) {
                 av[u][c] = mh_buf_load1(rs_r, inb[u] ? o0 + 4 * c : MH_OOB);
@@ -603,7 +685,7 @@ __global__ __launch_bounds__(256) void loss_tile_kernel(LossArgs p, int tiles_x,
             if (i >= LT_HH * LT_HW) break;
             const int ly = i / LT_HW, lx = i - ly * LT_HW;
             float r0v = 0.f, r1v = 0.f, r2v = 0.f, y0v = 0.f, y1v = 0.f, y2v = 0.f;
-            if (inb[u]) {
+            if (MASKED ? mv[u] != 0u : inb[u]) {
                 const float a0 = av[u][0] * s, a1 = av[u][1] * s, a2 = av[u][2] * s;
                 const float b0 = bv[u][0] * s, b1 = bv[u][1] * s, b2 = bv[u][2] * s;
                 const float w0 = w0v[u], w1 = w1v[u];
@@ -618,6 +700,7 @@ __global__ __launch_bounds__(256) void loss_tile_kernel(LossArgs p, int tiles_x,
             }
             s_rep[i * 3 + 0] = r0v; s_rep[i * 3 + 1] = r1v; s_rep[i * 3 + 2] = r2v;
             s_y[i * 3 + 0] = y0v; s_y[i * 3 + 1] = y1v; s_y[i * 3 + 2] = y2v;
+            if (MASKED) s_v[i] = (unsigned char)mv[u];
         }
     }
     __syncthreads();
@@ -628,7 +711,12 @@ __global__ __launch_bounds__(256) void loss_tile_kernel(LossArgs p, int tiles_x,
         const int ly = i / LT_WW, lx = i - ly * LT_WW;
         const int wy = y0t - 2 + ly, wx = x0t - 2 + lx;              // window (wy, wx) = halo pixels (ly .. ly+2, lx .. lx+2)
         float co[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
-        if ((unsigned)wy < (unsigned)Hw && (unsigned)wx < (unsigned)Ww) {
+        bool wok = (unsigned)wy < (unsigned)Hw && (unsigned)wx < (unsigned)Ww;
+        if (MASKED) {
+            const unsigned char* c = s_v + ly * LT_HW + lx;
+            wok = wok && (c[0] & c[1] & c[2] & c[LT_HW] & c[LT_HW + 1] & c[LT_HW + 2] & c[2 * LT_HW] & c[2 * LT_HW + 1] & c[2 * LT_HW + 2]) != 0;
+        }
+        if (wok) {
             const float C1 = 0.01f * 0.01f, C2 = 0.03f * 0.03f;
             float sx[3] = {0, 0, 0}, sy[3] = {0, 0, 0}, sxx[3] = {0, 0, 0}, syy[3] = {0, 0, 0}, sxy[3] = {0, 0, 0};
             for (int dy = 0; dy < 3; ++dy)
@@ -668,8 +756,9 @@ __global__ __launch_bounds__(256) void loss_tile_kernel(LossArgs p, int tiles_x,
     if (tid == 0) { p.part1[blockIdx.x] = tot1; p.part2[blockIdx.x] = tot2; }
     if (!with_grad) return;
     // ---- C -------------------------------------------------------------------------------------
-    const float k_ssim = 0.85f / ((float)p.B * (float)Hw * (float)Ww * 3.0f);
-    const float k_l1 = 0.15f / ((float)p.B * (float)p.H * (float)p.W * 3.0f);
+    // (MASKED: the counts are integers, so below 2^24 of them these are the unmasked factors of an all-ones mask; an empty set has no term)
+    const float k_ssim = MASKED ? (s_n[1] > 0 ? 0.85f / ((float)s_n[1] * 3.0f) : 0.f) : 0.85f / ((float)p.B * (float)Hw * (float)Ww * 3.0f);
+    const float k_l1 = MASKED ? (s_n[0] > 0 ? 0.15f / ((float)s_n[0] * 3.0f) : 0.f) : 0.15f / ((float)p.B * (float)p.H * (float)p.W * 3.0f);
     for (int i = tid; i < LT_H * LT_W; i += 256) {
         const int iy = i / LT_W, ix = i - iy * LT_W;
         const int y = y0t + iy, x = x0t + ix;
@@ -693,13 +782,25 @@ __global__ __launch_bounds__(256) void loss_tile_kernel(LossArgs p, int tiles_x,
             const float grep = k_ssim * (A[c] + Bc[c] * yv + Gc[c] * xv) + k_l1 * sgn;
             gd -= grep * s_drep[i * 3 + c];
         }
-        p.ddisp[((int64_t)b * p.H + y) * p.W + x] = gd * p.grad_scale;
+        p.ddisp[((int64_t)b * p.H + y) * p.W + x] = (MASKED && !s_v[(iy + 2) * LT_HW + ix + 2]) ? 0.f : gd * p.grad_scale;
     }
 }
 
-__global__ __launch_bounds__(256) void loss_final_kernel(LossArgs p) {
+// MASKED: the means run over the counts of loss_count_kernel (exact in float64); a term whose count is 0 is 0
+template <bool MASKED>
+__global__ __launch_bounds__(256) void loss_final_kernel(LossArgs p, LossMask m) {
     __shared__ double red[256];
     double a = 0.0, b = 0.0;
+    double c1 = 0.0, c2 = 0.0;
+    if (MASKED) {
+        for (int i = threadIdx.x; i < p.nblk1; i += 256) { c1 += (double)m.cnt[i]; c2 += (double)m.cnt[p.nblk1 + i]; }
+        red[threadIdx.x] = c1; __syncthreads();
+        for (int o = 128; o > 0; o >>= 1) { if ((int)threadIdx.x < o) red[threadIdx.x] += red[threadIdx.x + o]; __syncthreads(); }
+        c1 = red[0]; __syncthreads();
+        red[threadIdx.x] = c2; __syncthreads();
+        for (int o = 128; o > 0; o >>= 1) { if ((int)threadIdx.x < o) red[threadIdx.x] += red[threadIdx.x + o]; __syncthreads(); }
+        c2 = red[0]; __syncthreads();
+    }
     for (int i = threadIdx.x; i < p.nblk1; i += 256) a += (double)p.part1[i];
     for (int i = threadIdx.x; i < p.nblk2; i += 256) b += (double)p.part2[i];
     red[threadIdx.x] = a; __syncthreads();
@@ -708,9 +809,9 @@ __global__ __launch_bounds__(256) void loss_final_kernel(LossArgs p) {
     red[threadIdx.x] = b; __syncthreads();
     for (int o = 128; o > 0; o >>= 1) { if ((int)threadIdx.x < o) red[threadIdx.x] += red[threadIdx.x + o]; __syncthreads(); }
     if (threadIdx.x == 0) {
-        const double n1 = (double)p.B * p.H * p.W * 3.0;
-        const double n2 = (double)p.B * (p.H - 2) * (p.W - 2) * 3.0;
-        const double ms = red[0] / n2, ml = l1 / n1;
+        const double n1 = MASKED ? c1 * 3.0 : (double)p.B * p.H * p.W * 3.0;
+        const double n2 = MASKED ? c2 * 3.0 : (double)p.B * (p.H - 2) * (p.W - 2) * 3.0;
+        const double ms = (MASKED && c2 == 0.0) ? 0.0 : red[0] / n2, ml = (MASKED && c1 == 0.0) ? 0.0 : l1 / n1;
         p.result[0] = (float)(0.85 * ms + 0.15 * ml);
         p.result[1] = (float)ms;
         p.result[2] = (float)ml;
@@ -2706,9 +2807,43 @@ extern "C" int mh_reprojection_loss_phase(const float* left, const float* right,
     a.part1 = ws + 8 * n + 12 * nw; a.nblk1 = (int)ntiles;
     a.part2 = a.part1 + ntiles; a.nblk2 = (int)ntiles;
     hipStream_t s = (hipStream_t)stream;
-    if (phase != 2) hipLaunchKernelGGL(loss_tile_kernel, dim3((unsigned)ntiles), dim3(256), 0, s, a, tiles_x, tiles_y, ddisp ? 1 : 0);
-    if (phase != 1) hipLaunchKernelGGL(loss_final_kernel, dim3(1), dim3(256), 0, s, a);
+    if (phase != 2) hipLaunchKernelGGL(loss_tile_kernel<false>, dim3((unsigned)ntiles), dim3(256), 0, s, a, tiles_x, tiles_y, ddisp ? 1 : 0, LossMask{});
+    if (phase != 1) hipLaunchKernelGGL(loss_final_kernel<false>, dim3(1), dim3(256), 0, s, a, LossMask{});
     return mh_check_launch("reprojection_loss");
+}
+
+// The masks and the counts of the masked loss live in the retired map region of the loss workspace, behind the smoothness partial sums (one float per tile):
+//   [ smoothness: T floats | pad to 4 floats | left mask: n bytes | pad to 16 bytes | right mask: n bytes | pad to 16 bytes | counts: 2 T ints | ... ]
+// with n = B H W and T = loss_tiles <= n.  In floats: at most (T + 3) + 2 (n / 4 + 4) + 2 T <= 3.5 n + 11 <= 8 n for every n >= 9 (H, W >= 3).
+static inline int64_t loss_mask_floats(int64_t n) { return (n + 15) / 16 * 4; }
+extern "C" int64_t mh_loss_valid_offset(int32_t B, int32_t H, int32_t W) { return (loss_tiles(B, H, W) + 3) / 4 * 4; }
+
+extern "C" int mh_reprojection_loss_masked(const float* left, const float* right, const float* disp, const uint8_t* valid_l, const uint8_t* valid_r, float* ws,
+                                           float* result, float* ddisp, float grad_scale, int32_t B, int32_t H, int32_t W, int32_t phase, void* stream) {
+    MH_REQUIRE(phase >= 0 && phase <= 2, MH_ERR_ARG, "mh_reprojection_loss_masked: phase must be 0 (all), 1 (counts + maps + gradient) or 2 (final reduction)");
+    MH_REQUIRE(left && right && disp && ws && result, MH_ERR_ARG, "mh_reprojection_loss_masked: null argument");
+    MH_REQUIRE(valid_l && valid_r, MH_ERR_ARG, "mh_reprojection_loss_masked: null validity mask");
+    MH_REQUIRE(B > 0 && H >= 3 && W >= 3, MH_ERR_ARG, "mh_reprojection_loss_masked: image must be at least 3x3");
+    MH_REQUIRE(mh_aligned16(ws), MH_ERR_ALIGN, "mh_reprojection_loss_masked: workspace must be 16-byte aligned");
+    const int64_t n = (int64_t)B * H * W, nw = (int64_t)B * (H - 2) * (W - 2);
+    MH_REQUIRE(n * 12 < (1ll << 31) - 64, MH_ERR_ARG, "mh_reprojection_loss_masked: too many pixels (32-bit byte offsets into the frames)");
+    LossArgs a{};
+    a.left = left; a.right = right; a.disp = disp; a.result = result; a.ddisp = ddisp; a.grad_scale = grad_scale;
+    a.B = B; a.H = H; a.W = W;
+    const int tiles_x = mh_cdiv(W, LT_W), tiles_y = mh_cdiv(H, LT_H);
+    const int64_t ntiles = loss_tiles(B, H, W);
+    a.part1 = ws + 8 * n + 12 * nw; a.nblk1 = (int)ntiles;
+    a.part2 = a.part1 + ntiles; a.nblk2 = (int)ntiles;
+    const int64_t cnt_off = mh_loss_valid_offset(B, H, W) + 2 * loss_mask_floats(n);
+    MH_REQUIRE(cnt_off + 2 * ntiles <= 8 * n + 12 * nw, MH_ERR_ARG, "mh_reprojection_loss_masked: the counts do not fit in front of the partial sums");
+    const LossMask m{valid_l, valid_r, (int*)(ws + cnt_off)};
+    hipStream_t s = (hipStream_t)stream;
+    if (phase != 2) {
+        hipLaunchKernelGGL(loss_count_kernel, dim3((unsigned)ntiles), dim3(256), 0, s, a, tiles_x, tiles_y, m);
+        hipLaunchKernelGGL(loss_tile_kernel<true>, dim3((unsigned)ntiles), dim3(256), 0, s, a, tiles_x, tiles_y, ddisp ? 1 : 0, m);
+    }
+    if (phase != 1) hipLaunchKernelGGL(loss_final_kernel<true>, dim3(1), dim3(256), 0, s, a, m);
+    return mh_check_launch("reprojection_loss_masked");
 }
 
 // one partial sum per tile of smooth_tile_kernel: the tiling of the reprojection loss

@@ -205,6 +205,8 @@ SIGNATURES = {
     "mh_loss_ws_floats": (_L, [_I, _I, _I]),
     "mh_reprojection_loss": (_I, [_P, _P, _P, _P, _P, _P, _F, _I, _I, _I, _P]),
     "mh_reprojection_loss_phase": (_I, [_P, _P, _P, _P, _P, _P, _F, _I, _I, _I, _I, _P]),
+    "mh_loss_valid_offset": (_L, [_I, _I, _I]),
+    "mh_reprojection_loss_masked": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _F, _I, _I, _I, _I, _P]),
     "mh_smoothness_ws_floats": (_L, [_I, _I, _I]),
     "mh_smoothness_loss": (_I, [_P, _P, _P, _P, _P, _F, _F, _I, _I, _I, _I, _I, _I, _P]),
     "mh_metrics_ws_floats": (_L, [_I, _I, _I]),
@@ -242,7 +244,7 @@ SIGNATURES = {
     "mh_event_destroy": (_I, [_P]),
     "mh_stream_sync": (_I, [_P]),
 }
-_NO_STATUS = {"mh_comm_available", "mh_deterministic_overflow", "mh_bias_grad_blocks", "mh_tune_conv_bank_small", "mh_conv_image_ok", "mh_level_front_head_ok", "mh_deterministic_ranges", "mh_planes_kc16", "mh_conv2d_planes_bwd_ok", "mh_stamp_rate_khz", "mh_pack32_bytes", "mh_conv2d_planes_ok", "mh_tune_conv_planes", "mh_tune_wgrad_target_pct", "mh_tune_wgrad_image", "mh_conv2d_takes_shadows", "mh_conv2d_takes_bank", "mh_conv_bank_small_maxpix", "mh_tune_conv_bank_tile", "mh_tune_conv_rows", "mh_last_error", "mh_last_kernel", "mh_tune_conv_bank", "mh_pack_bytes", "mh_abi_version", "mh_tune_conv_patch", "mh_crc32c", "mh_device_count", "mh_loss_ws_floats", "mh_smoothness_ws_floats", "mh_metrics_ws_floats", "mh_proxy_ws_floats", "mh_proxy_scaled_ws_floats", "mh_metrics_kitti_ws_floats", "mh_frame_prepare_ws_floats", "mh_sgm_ws_bytes", "mh_sgm_ws_bytes_ex", "mh_sgm_ws_bytes_scaled", "mh_sgm_speckle_ws_bytes", "mh_colorize_ws_bytes"}
+_NO_STATUS = {"mh_comm_available", "mh_deterministic_overflow", "mh_bias_grad_blocks", "mh_tune_conv_bank_small", "mh_conv_image_ok", "mh_level_front_head_ok", "mh_deterministic_ranges", "mh_planes_kc16", "mh_conv2d_planes_bwd_ok", "mh_stamp_rate_khz", "mh_pack32_bytes", "mh_conv2d_planes_ok", "mh_tune_conv_planes", "mh_tune_wgrad_target_pct", "mh_tune_wgrad_image", "mh_conv2d_takes_shadows", "mh_conv2d_takes_bank", "mh_conv_bank_small_maxpix", "mh_tune_conv_bank_tile", "mh_tune_conv_rows", "mh_last_error", "mh_last_kernel", "mh_tune_conv_bank", "mh_pack_bytes", "mh_abi_version", "mh_tune_conv_patch", "mh_crc32c", "mh_device_count", "mh_loss_ws_floats", "mh_loss_valid_offset","mh_smoothness_ws_floats", "mh_metrics_ws_floats", "mh_proxy_ws_floats", "mh_proxy_scaled_ws_floats", "mh_metrics_kitti_ws_floats", "mh_frame_prepare_ws_floats", "mh_sgm_ws_bytes", "mh_sgm_ws_bytes_ex", "mh_sgm_ws_bytes_scaled", "mh_sgm_speckle_ws_bytes", "mh_colorize_ws_bytes"}
 
 
 class MadnetHipError(RuntimeError):

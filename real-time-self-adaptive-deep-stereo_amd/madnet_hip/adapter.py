@@ -35,7 +35,7 @@ class Adapter(object):
                  num_blocks=1, fixed_id=0, sample_frequency=1, ssim_th=0.5, reprojection_scale=1,
                  use_graph=True, shared_model=False, process_group=None, loss="reprojection", dilation=1, decay=0.99, uf=0.01,
                  optimizer="momentum", reset_optimizer=False, reward_every_step_first=False, early_reduce=None, in_graph_collective=None, fetch_inputs=None,
-                 kitti_metrics=False, proxy_loss="mean_l1", smoothness=0.0):
+                 kitti_metrics=False, proxy_loss="mean_l1", smoothness=0.0, valid_masks=None):
         """loss='proxy', dilation, decay, uf: the continual-adaptation variant (Stereo_Continual_Adaptation.py:75-112,
         205-249, 302-304): proxy-label mean_l1 loss, weight update only every `dilation`-th frame, reward update
         sample_distribution = decay * sample_distribution (+ uf * gain on the last trained blocks).
@@ -46,6 +46,10 @@ class Adapter(object):
         frame, added to every reprojection loss of the step -- the full-resolution one and the MAD blocks', at reprojection_scale on the resized prediction and
         frame like the loss it joins.  The loss that is minimised is the loss that is watched: out['loss'], the reset test against ssim_th and the MAD reward read
         the sum; out['smoothness'] = w * S of the full-resolution prediction.  0 (default): every plan is what it is without the keyword.
+        valid_masks (loss='reprojection', reprojection_scale 1 only): (valid_l, valid_r), uint8 [B,H,W], non-zero = the pixel exists (Rectifier.valid_masks: the
+        wedges of a rectified frame and the zeros of crop_or_pad do not).  Every reprojection loss of the step -- the full-resolution one and the MAD blocks' --
+        then runs over the valid pixels only (mh_reprojection_loss_masked); out['loss'], the reset test against ssim_th and the MAD reward read that value.
+        set_valid_masks(l, r) replaces the masks later, also under a captured graph.  None (default): every plan is what it is without the keyword.
         optimizer='adam', reset_optimizer, reward_every_step_first: the live demo's variant of the loop (Demo/demo_model.py:164,
         203-208, 253-262): tf.train.AdamOptimizer(lr) instead of momentum; a reset without a weight file re-runs the initialisers,
         i.e. also clears the optimizer slots; its `first` flag is never cleared, so every step re-seeds both remembered losses.
@@ -72,6 +76,13 @@ class Adapter(object):
             raise NotImplementedError("the smoothness term needs an engine that records it")
         if hasattr(self.eng, "smoothness"):
             self.eng.smoothness = self.smoothness       # (before the first plan is built: the weight is a slot of the LOSS records)
+        if valid_masks is not None:
+            if loss == "proxy":
+                raise ValueError("valid_masks needs loss='reprojection' (the label losses have their own valid set)")
+            if reprojection_scale != 1:
+                raise NotImplementedError("valid_masks with reprojection_scale != 1: the blocks' losses run on resized frames")
+            if not hasattr(self.eng, "set_valid_masks"):
+                raise NotImplementedError("valid_masks needs an engine that records the masked loss")
         if loss == "proxy":
             if not hasattr(self.eng, "proxy"):
                 raise NotImplementedError("the proxy-label loss needs an engine with a proxy buffer")
@@ -146,8 +157,25 @@ class Adapter(object):
         # pinned read-back buffer: [loss result (4) | EPE / bad3 (4)], with kitti_metrics [loss result (4) | KITTI report (4) | EPE / bad3 (4)]
         self._host = torch.zeros(12 if self.kitti else 8, pin_memory=self.cuda)
         self._o_met = 8 if self.kitti else 4
+        if valid_masks is not None:
+            self.set_valid_masks(*valid_masks)
 
     # -------------------------------------------------------------------------------------------
+    def set_valid_masks(self, valid_l, valid_r):
+        """the validity masks of the reprojection losses (Adapter(valid_masks=)).  The first call must come before the first step (a plan's LOSS records either
+        carry the masked flag or do not); later calls rewrite the mask bytes in the engine's loss workspaces on the adapter's stream, so the next step -- a
+        replay of the captured graph included -- reads the new masks."""
+        if self.loss == "proxy":
+            raise ValueError("valid_masks needs loss='reprojection' (the label losses have their own valid set)")
+        if getattr(self.eng, "rscale", 1) != 1:
+            raise NotImplementedError("valid_masks with reprojection_scale != 1: the blocks' losses run on resized frames")
+        if not hasattr(self.eng, "set_valid_masks"):
+            raise NotImplementedError("valid_masks needs an engine that records the masked loss")
+        if self.eng.valid is None and self._plans:
+            raise RuntimeError("set_valid_masks: the first call must come before the first step")
+        with (torch.cuda.stream(self.stream) if self.cuda else _null()):
+            self.eng.set_valid_masks(valid_l, valid_r)
+
     def _plan(self, key):
         if key not in self._plans:
             eng = self.eng

@@ -65,6 +65,42 @@ class EngineBase(object):
                 dst = getattr(self, name)
                 dst.copy_(torch.as_tensor(src, dtype=torch.float32).reshape(dst.shape))
 
+    # validity masks of the reprojection losses (rectified frames: Rectifier.valid_masks) ----------------------------------------------------
+    valid = None                    # (valid_l, valid_r) once set_valid_masks was called: every LOSS record carries MH_LOSS_MASKED
+    _loss_recorded = False          # a reprojection loss was recorded (without masks, if valid is None)
+    LOSS_WORKSPACES = ("loss_ws", "loss_ws_k")      # the full-resolution loss's and the MAD blocks'
+
+    def _loss_valid(self):
+        """`valid` of the reprojection loss being recorded"""
+        self._loss_recorded = True
+        return self.valid
+
+    def set_valid_masks(self, valid_l, valid_r):
+        """which pixels of the frames exist: uint8 [B,H,W] (or [H,W] for B = 1), non-zero = valid.  The reprojection losses recorded from now on run over the valid
+        pixels only (mh_reprojection_loss_masked); the masks are copied, on the CURRENT stream, into every loss workspace of this engine.  The first call must
+        come before the first plan is built (a recorded LOSS op either carries the flag or does not); later calls only rewrite the bytes -- also between two
+        replays of a captured plan."""
+        if getattr(self, "loss_kind", "reprojection") != "reprojection":
+            raise ValueError("validity masks need loss_kind 'reprojection' (the label losses have their own valid set)")
+        if getattr(self, "rscale", 1) != 1:
+            raise NotImplementedError("validity masks with a reprojection scale != 1: the blocks' losses run on resized frames")
+        if self.valid is None and self._loss_recorded:
+            raise RuntimeError("set_valid_masks: the first call must come before the first plan is built")
+        shape = (self.B, self.H0, self.W0)
+        masks = []
+        for m in (valid_l, valid_r):
+            m = torch.as_tensor(m)
+            if m.dtype != torch.uint8 or m.numel() != self.B * self.H0 * self.W0:
+                raise ValueError("validity masks: uint8 tensors of shape %s" % (shape,))
+            masks.append(m.to(self.dev).reshape(shape).contiguous())
+        if self.valid is None:
+            self.valid = tuple(torch.empty(shape, dtype=torch.uint8, device=self.dev) for _ in masks)
+        for dst, m in zip(self.valid, masks):
+            dst.copy_(m)
+        for name in self.LOSS_WORKSPACES:
+            if getattr(self, name, None) is not None:
+                ops.loss_set_valid(self.lib, getattr(self, name), *self.valid)
+
     def record_metrics(self, r):
         """EPE / bad3 of the step's disparity (Stereo_Online_Adaptation.py:74-82) and, with kitti_metrics, the continual loop's report -- EPE over gt > 0 and
         KITTI D1-all (Stereo_Continual_Adaptation.py:245-249) -- on the same lane, into params.res_kitti"""

@@ -354,7 +354,7 @@ class DispNetEngine(EngineBase):
         if self.loss_kind == "proxy":
             ops.proxy_loss(r, self.pred, self.proxy, self.proxy_ws, self.res_loss, self.dpred if with_grad else None, weight=0.01, loss=self.proxy_loss)
         else:
-            ops.reprojection_loss(r, self.left, self.right, self.pred, self.loss_ws, self.res_loss, self.dpred if with_grad else None, smoothness=self.smoothness)
+            ops.reprojection_loss(r, self.left, self.right, self.pred, self.loss_ws, self.res_loss, self.dpred if with_grad else None, smoothness=self.smoothness, valid=self._loss_valid())
         self.record_metrics(r)
 
     # ---- backward (derived from the op list) ------------------------------------------------------------

@@ -161,6 +161,8 @@ class MadNetEngine(EngineBase, ElisionPasses, BackwardRecorder):
         s = int(s)
         if s < 1:
             raise ValueError("reprojectionScale must be >= 1")
+        if s != 1 and self.valid is not None:
+            raise NotImplementedError("validity masks with a reprojection scale != 1: the blocks' losses run on resized frames")
         self.rscale = s
         self._scale_bufs = None
         self._ensure_scale_buffers()
@@ -499,17 +501,17 @@ class MadNetEngine(EngineBase, ElisionPasses, BackwardRecorder):
             # only the maps + the gradient are on the critical path; the reduction of the loss VALUE and the validation metrics
             # (read by the host after the step) run on a side lane next to the backward pass
             ops.reprojection_loss(r, self.left, self.right, self.pred, self.loss_ws, self.res_loss,
-                                  self.dpred if with_grad else None, phase=1, smoothness=self.smoothness)
+                                  self.dpred if with_grad else None, phase=1, smoothness=self.smoothness, valid=self._loss_valid())
         else:
             ops.reprojection_loss(r, self.left, self.right, self.pred, self.loss_ws, self.res_loss,
-                                  self.dpred if with_grad else None, smoothness=self.smoothness)
+                                  self.dpred if with_grad else None, smoothness=self.smoothness, valid=self._loss_valid())
         if side:
             r.lane = 1
             try:
                 self._stamp(r, "side_lane_first_op")
                 self._flush_x0(r)               # (the padded frames: read by conv1's filter gradient only, on this lane, at the far end of the step)
                 if self.loss_kind != "proxy":
-                    ops.reprojection_loss(r, self.left, self.right, self.pred, self.loss_ws, self.res_loss, None, phase=2, smoothness=self.smoothness)
+                    ops.reprojection_loss(r, self.left, self.right, self.pred, self.loss_ws, self.res_loss, None, phase=2, smoothness=self.smoothness, valid=self._loss_valid())
                 self.record_metrics(r)
             finally:
                 r.lane = 0
@@ -719,7 +721,7 @@ class MadNetEngine(EngineBase, ElisionPasses, BackwardRecorder):
                         ops.resize_bwd(r, self.dp_s, self.disp_k[lv], self.ddisp_k, Hs, Ws, mul=1.0, mode=0)
                     else:
                         ops.reprojection_loss(r, self.left, self.right, self.disp_k[lv], self.loss_ws_k, self.res_loss_k,
-                                              self.ddisp_k, smoothness=self.smoothness)
+                                              self.ddisp_k, smoothness=self.smoothness, valid=self._loss_valid())
                     self.record_backward(r, lv, bv, bulkhead=True)
                 if collective is not None:
                     # the block's gradient ranges + the loss tail (behind the gradient buffer) as ONE RCCL group between the block's backward pass and its update

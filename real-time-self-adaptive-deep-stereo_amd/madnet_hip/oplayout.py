@@ -37,6 +37,8 @@ CONV_SHADOW_ONLY = 4        # the fp32 result is not stored
 CONV_IN_F32_STALE = 8       # the fp32 input was not stored: refused unless the dispatched kernel stages the shadow
 CONV_MASK_F32_STALE = 16    # likewise the fp32 mask
 CONV_OUT_PLANES = 32        # p[7] / p[5] are the hi / lo planes of the result (mh_conv2d_sh4)
+# OP_LOSS, `phase` slot (MH_LOSS_MASKED): phase | LOSS_MASKED = mh_reprojection_loss_masked, its validity masks at mh_loss_valid_offset of the record's own ws (Recorder.loss_masked)
+LOSS_MASKED = 4
 
 # ---- the prefix the conv kinds share: the mh_conv_desc ints in slots 0 .. 20, precision in 22, alpha / mask_alpha in f ----------------------------------
 DESC_I = "B Hi Wi Ho Wo K N kh kw stride dil pad_t pad_l mode w_trans in_ld out_ld mask_ld accumulate mask_c0 mask_c1"

@@ -872,8 +872,27 @@ def smoothness_loss(lib, disp, image, ws, result, ddisp=None, weight=1.0, grad_s
     lib.smoothness_loss(_p(disp), _p(image), _p(ws), _p(result), _p(ddisp), float(weight), grad_scale, int(bool(accumulate)), B, H, W, Cc, phase, _p(stream))
 
 
-def reprojection_loss(lib, left, right, disp, ws, result, ddisp=None, grad_scale=1.0, stream=None, phase=0, smoothness=0.0):
+def loss_set_valid(lib, ws, valid_l, valid_r):
+    """copy the validity masks (uint8 [B,H,W], non-zero = valid) of a masked LOSS record into its workspace `ws`: the left mask at float offset
+    mh_loss_valid_offset, the right one at the next 16-byte boundary (include/madnet_hip.h).  A torch copy on the current stream; the bytes may be rewritten
+    between two replays of a captured plan."""
+    B, H, W = valid_l.shape
+    if valid_r.shape != valid_l.shape or valid_l.dtype != torch.uint8 or valid_r.dtype != torch.uint8:
+        raise ValueError("validity masks: two uint8 tensors of one shape [B,H,W]")
+    n = B * H * W
+    if ws.numel() < int(lib.loss_ws_floats(B, H, W)):
+        raise ValueError("validity masks: the workspace is smaller than mh_loss_ws_floats(%d, %d, %d)" % (B, H, W))
+    raw = ws.view(torch.uint8)
+    o = 4 * int(lib.loss_valid_offset(B, H, W))
+    raw[o:o + n].copy_(valid_l.reshape(-1))
+    o += (n + 15) // 16 * 16
+    raw[o:o + n].copy_(valid_r.reshape(-1))
+
+
+def reprojection_loss(lib, left, right, disp, ws, result, ddisp=None, grad_scale=1.0, stream=None, phase=0, smoothness=0.0, valid=None):
     """phase 0 = everything; 1 = warp + SSIM maps + gradient (what the backward pass waits for); 2 = the reduction of the loss value.
+    valid: (valid_l, valid_r), uint8 [B,H,W]: the loss over the valid pixels (mh_reprojection_loss_masked).  Recorded: the flag in the LOSS record's `phase` slot
+    (the recorder's state attribute `loss_masked`, put back afterwards) -- the replay reads the masks from ws (loss_set_valid), not from these tensors.
     smoothness: weight w of the edge-aware smoothness term of (disp, left): result[0] += w * S, result[3] = w * S (result then has 4 floats), ddisp += its
     gradient, each in the phase that writes the reprojection loss's share.  Recorded: the weight in the LOSS record's `smooth_weight` slot (the recorder's state
     attribute, put back afterwards); launched: the second call made here, its partial sums in the first floats of ws.  0: nothing more is launched or recorded."""
@@ -882,14 +901,18 @@ def reprojection_loss(lib, left, right, disp, ws, result, ddisp=None, grad_scale
     recording = hasattr(lib, "note_refs")          # a plan.Recorder
     if recording:
         before, lib.smoothness = lib.smoothness, smoothness
+        masked_before, lib.loss_masked = lib.loss_masked, valid is not None
     try:
-        if phase == 0:
+        if valid is not None and not recording:
+            lib.reprojection_loss_masked(_p(left), _p(right), _p(disp), _p(valid[0]), _p(valid[1]), _p(ws), _p(result), _p(ddisp), grad_scale, B, H, W, phase, _p(stream))
+        elif phase == 0:
             lib.reprojection_loss(_p(left), _p(right), _p(disp), _p(ws), _p(result), _p(ddisp), grad_scale, B, H, W, _p(stream))
         else:
             lib.reprojection_loss_phase(_p(left), _p(right), _p(disp), _p(ws), _p(result), _p(ddisp), grad_scale, B, H, W, phase, _p(stream))
     finally:
         if recording:
             lib.smoothness = before
+            lib.loss_masked = masked_before
     if smoothness != 0.0 and not recording:
         lib.smoothness_loss(_p(disp), _p(left), _p(ws), _p(result), _p(ddisp), smoothness, grad_scale, 1, B, H, W, 3, phase, _p(stream))
 

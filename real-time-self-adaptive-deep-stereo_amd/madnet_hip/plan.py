@@ -28,6 +28,7 @@ class Recorder(object):
         self.wgrad_group_max_m = 0  # grouped filter-gradient launches: pixel cap of this plan's layers (0 = library default)
         self.label_loss = 0         # the `loss` slot of the PROXY_LOSS / PROXY_LOSS_SCALED ops recorded next (_ffi.LABEL_LOSS; 0 = mean_l1, today's entry points)
         self.smoothness = 0.0       # the `smooth_weight` slot of the LOSS ops recorded next: weight of the edge-aware smoothness term (0 = the reprojection loss alone)
+        self.loss_masked = False    # True: the LOSS ops recorded next carry oplayout.LOSS_MASKED in their `phase` slot (validity masks in their workspace: ops.loss_set_valid)
         self.work = {}              # op index -> (algorithmic flops, bytes) of the multi-layer ops (a streamed filter-gradient batch)
         self._pending_work = [0.0, 0.0]
         self.cuts = []              # op indices where compile_parts() splits the recording (a collective goes between the parts)
@@ -216,7 +217,7 @@ class Recorder(object):
         self.reprojection_loss_phase(left, right, disp, ws, result, ddisp, grad_scale, B, H, W, 0, stream)
 
     def reprojection_loss_phase(self, left, right, disp, ws, result, ddisp, grad_scale, B, H, W, phase, stream):
-        self._op(_ffi.OP_LOSS, locals(), smooth_weight=self.smoothness)
+        self._op(_ffi.OP_LOSS, locals(), smooth_weight=self.smoothness, phase=phase | (oplayout.LOSS_MASKED if self.loss_masked else 0))
 
     def proxy_loss(self, pred, proxy, ws, result, dpred, weight, grad_scale, B, H, W, stream):
         self._op(_ffi.OP_PROXY_LOSS, locals(), loss=self.label_loss)

@@ -75,6 +75,25 @@ def load_calibration(calibration):
         return json.load(f_in), os.path.dirname(os.path.abspath(calibration))
 
 
+def crop_or_pad(x, th, tw):
+    """tf.image.resize_image_with_crop_or_pad on a [B,h,w,c] device tensor (Demo/demo_model.py:84-86): centre crop with offset
+    (in - target)//2, centre zero pad with (target - in)//2 in front."""
+    h, w = x.shape[1], x.shape[2]
+    if h > th:
+        o = (h - th) // 2
+        x = x[:, o:o + th]
+    if w > tw:
+        o = (w - tw) // 2
+        x = x[:, :, o:o + tw]
+    h, w = x.shape[1], x.shape[2]
+    if h < th or w < tw:
+        out = x.new_zeros(x.shape[0], th, tw, x.shape[3])
+        pt, pl = (th - h) // 2, (tw - w) // 2
+        out[:, pt:pt + h, pl:pl + w] = x
+        x = out
+    return x
+
+
 class Rectifier(object):
     """Builds the sampling map of both views once, at construction (on the current stream), and owns it.  apply(frames): [2,h,w,c] uint8 or float32 device
     tensor of raw frames (left first; c = 1, 3 or 4) -> [2,Ho,Wo,3] float32 on the frames' scale, zero where a rectified pixel has no source."""
@@ -133,3 +152,20 @@ class Rectifier(object):
             out = self.new_output()
         ops.remap(self.lib, frames.contiguous(), self.map, out, stream=self._stream())
         return out
+
+    def valid_masks(self, image_shape=None, crop_shape=None):
+        """(valid_l, valid_r), uint8 [1,H,W] on the device: which pixels of the frames the network sees show something -- for Adapter(valid_masks=).  Set-up
+        time, in torch.  A rectified pixel is valid when its map position lies inside the raw view, 0 <= mx <= Ws - 1 and 0 <= my <= Hs - 1 (there mh_remap
+        reads four taps of the source; outside it blends in zeros).  That 0/1 image then goes the frames' way -- rescale_image to image_shape, crop_or_pad to
+        crop_shape (None: the step is skipped, as in the demo) -- and a pixel stays valid when the result is >= 1 - 1e-5: the zeros of the pad are invalid, and so
+        is every pixel an invalid one contributes to with noticeable weight."""
+        Hs, Ws = self.size
+        mx, my = self.map[..., 0], self.map[..., 1]
+        x = ((mx >= 0) & (mx <= Ws - 1) & (my >= 0) & (my <= Hs - 1)).to(torch.float32)[..., None]          # [2,Ho,Wo,1]
+        if image_shape is not None and (x.shape[1], x.shape[2]) != (int(image_shape[0]), int(image_shape[1])):
+            from Data_utils import preprocessing
+            x = preprocessing.rescale_image(x, image_shape)
+        if crop_shape is not None:
+            x = crop_or_pad(x, int(crop_shape[0]), int(crop_shape[1]))
+        v = (x[..., 0] >= 1.0 - 1e-5).to(torch.uint8).contiguous()
+        return v[:1], v[1:]
